@@ -6,7 +6,16 @@ columns ({vm, rom} layout), blowup 16, q 64, grind 16, partitions (4, 16).  One 
 full segment proof per rank (trace LDE, constraint evaluation, composition, DEEP, FRI,
 grinding, queries, Proof::to_bytes) with the trace already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--segments S] [--dry-run]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--segments S] [--dry-run]
+
+A plain run sets up, warms up, times the K steps, checks the last proof against the committed
+golden and prints the result line (value = N x K / seconds, ms_per_step = one timed step).
+--dump-outputs DIR then writes the last timed proof (the bytes a caller of the timed path
+receives) as DIR/proof.npy (float32, one element per byte; proof_rank<r>.npy per rank when N > 1);
+the segment is synthesised from a fixed seed, so two builds can be compared byte for byte.
+Everything else described below (the per-family kernel breakdown from an extra untimed proof,
+the step hand-off, host_trace, configs[2]..[4], the real programs, cpu_baseline) runs only
+with --full.
 
 Ranks.  N > 1 runs one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE set)
 this process is one rank and WORLD_SIZE must equal --gpus.  Started directly with --gpus N > 1
@@ -25,7 +34,7 @@ Parity.  Every rank hashes its last proof and compares it with the committed CPU
 golden of its segment (tests/golden/proof_2p16.json, make_proof_goldens.py); at N = 1 the
 cpu_baseline leg also proves the same segment on the oracle and compares the bytes.
 
-Other lines: configs[2] (8 distinct segments on one GPU, 1/2/4 contexts in flight), configs[3]
+Other lines (--full): configs[2] (8 distinct segments on one GPU, 1/2/4 contexts in flight), configs[3]
 shape (--segments S distinct segments sharded over the ranks, each rank pipelining its share,
 then the step-proof gather and children root on rank 0; default S = 8 x N when N > 1),
 configs[4] (one 2^20-row segment per rank: replicas, max-over-ranks time) and the real program
@@ -271,6 +280,13 @@ def load_traffic(kernel):
     return None
 
 
+def dump_outputs(directory, name, proof):
+    """--dump-outputs: the last timed proof, one float32 element per byte, as <directory>/<name>.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float32))
+
+
 # ------------------------------------------------------------------------ launcher
 def free_port():
     s = socket.socket()
@@ -303,7 +319,7 @@ def spawn_ranks(n):
 
 def lines_for_rank(args, world):
     """The bench lines every rank takes part in (the --dry-run report; main() runs the same)."""
-    lines = ["headline", "step_handoff"]
+    lines = ["headline"] + (["step_handoff"] if args.full else [])
     n_seg = args.segments if args.segments >= 0 else (8 * world if world > 1 else 0)
     if n_seg > 0:
         lines.append("c4_sharded")
@@ -832,9 +848,20 @@ def main():
     ap.add_argument("--tuning", default="spin,malloc",
                     help="opt-in process settings this process applies (zkl_hip_process_tuning): spin, malloc, none")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rank plumbing only, no device work (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every line besides the headline (kernel breakdown, step hand-off, host_trace, "
+                         "configs[2]..[4], real programs, cpu_baseline); their options below apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed proof as DIR/proof.npy (float32, one element per byte)")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline only
+        args.c3_segments = args.segments = args.c5_log_n = args.program_steps = args.host_steps = 0
+        args.programs, args.no_cpu_baseline = "none", True
     if args.gpus < 1:
         log("bench: --gpus must be >= 1")
+        return 2
+    if args.steps < 1 or args.warmup < 0:  # ms_per_step and --dump-outputs need one timed proof
+        log("bench: --steps must be >= 1 and --warmup >= 0")
         return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
@@ -921,11 +948,13 @@ def main():
         proof = bytes(pbuf[:plen])  # the last timed proof, checked below
     host = ctx.host_times()
     parity = dist.gather_to_root(parity_of(proof, seed, log_n))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "proof" if world == 1 else f"proof_rank{rank}", proof)
     stages, fam = {}, {}
     # Inside the timed region only the dominant family (the trace row hash) is bracketed by
     # HIP events (each bracket costs ~10 us of queue time); one extra untimed proof with
     # every family bracketed gives the per-family breakdown.
-    if rank == 0:
+    if rank == 0 and args.full:
         ctx.set_kernel_timing(2)
         ctx.prove_segment_device(d_trace, W, n, pi, opts)
         fam = ctx.kernel_times()
@@ -953,7 +982,7 @@ def main():
                      "per_proof_allocation": fresh}
     del trace
     ctx.close()
-    hand, _ = handoff(zkl_hip, dist, [(rank, pi, proof)], world, device=device)
+    hand = handoff(zkl_hip, dist, [(rank, pi, proof)], world, device=device)[0] if args.full else None
 
     # configs[3] shape: S distinct segments sharded over the ranks, pipelined per rank
     c4 = None
@@ -1076,16 +1105,17 @@ def main():
                 "note": "VALU-issue bound (integer Poseidon); see roofline_valu",
             },
             "roofline_valu": valu_roofline(perms_per_s),
-            "dominant_kernel_family": dom,
-            "kernel_ms_per_family_untimed_step": {k: round(v[0], 3) for k, v in fam.items()},
-            "kernel_launches_per_family_untimed_step": {k: v[1] for k, v in fam.items()},
-            "stage_ms_untimed_step": {k: round(v, 3) for k, v in stages.items()},
+            **({"dominant_kernel_family": dom,
+                "kernel_ms_per_family_untimed_step": {k: round(v[0], 3) for k, v in fam.items()},
+                "kernel_launches_per_family_untimed_step": {k: v[1] for k, v in fam.items()},
+                "stage_ms_untimed_step": {k: round(v, 3) for k, v in stages.items()}} if args.full else {}),
             "host_ms_last_step": {k: round(v, 3) for k, v in host.items()},
             "call_ms_each_step": [round(v, 2) for v in step_ms],
             # stalled-step check: slowest step over the median step
             "max_over_median_step": round(max(step_ms) / sorted(step_ms)[len(step_ms) // 2], 3) if step_ms else None,
             **({"stage_ms_each_step": step_stages} if step_stages else {}),
-            "step_handoff": hand,
+            **({"step_handoff": hand} if args.full else {}),
+            "full": args.full,
         }
         if c4 is not None:
             out["c4_sharded"] = c4

@@ -6,7 +6,7 @@ set -u
 tag=$1; shift
 out=gpurun_out/$tag
 mkdir -p $out
-B="bench.py --steps 3 --warmup 1 --no-cpu-baseline --c5-log-n 0 --c3-inflight 1,2,4,6"
+B="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --c5-log-n 0 --c3-inflight 1,2,4,6"
 run() {  # name, then env assignments / library
   local n=$1; shift
   ( for a in "$@"; do case $a in *.so) export ZKL_HIP_LIB=$a ;; *) export "$a" ;; esac; done

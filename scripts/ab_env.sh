@@ -21,7 +21,7 @@ done
 for rep in 1 2; do
   for spec in "$@"; do
     name=${spec%%=*}
-    env $(run_env "$spec") timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 --host-steps 0 > $out/bench_${name}_$rep.json 2> $out/bench_$name.err || { echo "bench $name failed"; tail -5 $out/bench_$name.err; exit 1; }
+    env $(run_env "$spec") timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 --host-steps 0 > $out/bench_${name}_$rep.json 2> $out/bench_$name.err || { echo "bench $name failed"; tail -5 $out/bench_$name.err; exit 1; }
     python3 -c "import json; d=json.load(open('$out/bench_${name}_$rep.json')); k=d['kernel_ms_per_family_untimed_step']; print('$name', d['ms_per_step'], d['parity']['status'], 'rows', d['roofline']['avg_launch_ms'], 'ntt', k['ntt'], 'ce', k['constraint_eval'], 'deep', k['deep'], 'merkle', k['merkle'], 'comp', k['comp_hash_rows'], 'fri', k['fri'])"
   done
 done

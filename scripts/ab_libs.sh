@@ -14,7 +14,7 @@ done
 for rep in 1 2; do
   for v in zk-lisp_amd/zkl_hip/libzkl_hip.so "$@"; do
     t=$(basename $v .so)
-    ZKL_HIP_LIB=$v timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 > $out/bench_${t}_$rep.json 2> $out/bench_$t.err || { echo "bench $t failed"; tail -5 $out/bench_$t.err; exit 1; }
+    ZKL_HIP_LIB=$v timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 > $out/bench_${t}_$rep.json 2> $out/bench_$t.err || { echo "bench $t failed"; tail -5 $out/bench_$t.err; exit 1; }
     python3 -c "import json; d=json.load(open('$out/bench_${t}_$rep.json')); print('$t', d['ms_per_step'], d['parity']['status'], d['kernel_ms_per_family_untimed_step']['ntt'], d['stage_ms_untimed_step']['trace_lde'])"
   done
 done

@@ -15,7 +15,7 @@ done
 for rep in 1 2; do
   for v in "$@"; do
     t=$(basename $v .so)
-    ZKL_HIP_LIB=$v timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 --host-steps 0 > $out/bench_${t}_$rep.json 2> $out/bench_$t.err || { echo "bench $t failed"; tail -5 $out/bench_$t.err; exit 1; }
+    ZKL_HIP_LIB=$v timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 --host-steps 0 > $out/bench_${t}_$rep.json 2> $out/bench_$t.err || { echo "bench $t failed"; tail -5 $out/bench_$t.err; exit 1; }
     python3 -c "import json; d=json.load(open('$out/bench_${t}_$rep.json')); k=d['kernel_ms_per_family_untimed_step']; print('$t', d['ms_per_step'], d['parity']['status'], 'rows', d['roofline']['avg_launch_ms'], 'merkle', k['merkle'], 'comp', k['comp_hash_rows'], 'fri', k['fri'])"
   done
 done

@@ -6,7 +6,7 @@ set -u
 tag=$1; shift
 out=gpurun_out/$tag
 mkdir -p $out
-B="bench.py --steps 10 --warmup 3 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 --host-steps 0 --program-steps 0 --programs none"
+B="bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 --host-steps 0 --program-steps 0 --programs none"
 for rep in 1 2 3; do
   for v in "$@"; do
     n=$(basename $v .so)

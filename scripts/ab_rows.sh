@@ -19,6 +19,6 @@ for rep in 1 2; do
 done
 for v in "$@"; do
   tag=$(basename $v .so)
-  ZKL_HIP_LIB=$v timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 > $out/bench_$tag.json 2> $out/bench_$tag.err || { echo "bench $tag failed"; tail -5 $out/bench_$tag.err; exit 1; }
+  ZKL_HIP_LIB=$v timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --c3-segments 0 --c5-log-n 0 > $out/bench_$tag.json 2> $out/bench_$tag.err || { echo "bench $tag failed"; tail -5 $out/bench_$tag.err; exit 1; }
   python3 -c "import json; d=json.load(open('$out/bench_$tag.json')); print('$tag', d['ms_per_step'], d['parity']['status'], d['kernel_ms_per_family_untimed_step'])"
 done

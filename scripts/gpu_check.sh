@@ -7,7 +7,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1 || { echo "pytest gpu failed rc=$?"; tail -30 $out/pytest_gpu.log; exit 1; }
 tail -2 $out/pytest_gpu.log
-timeout -k 10 600 python bench.py --steps 3 --warmup 1 > $out/bench.json 2> $out/bench.err || { echo "bench failed rc=$?"; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 > $out/bench.json 2> $out/bench.err || { echo "bench failed rc=$?"; tail -20 $out/bench.err; exit 1; }
 cat $out/bench.json
 export TMPDIR=/tmp
 root=$PWD

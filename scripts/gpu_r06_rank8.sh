@@ -9,7 +9,7 @@ out=gpurun_out/r06_rank8
 mkdir -p $out
 ( while true; do date +%s >> $out/mem.txt; grep -E "MemAvailable|Mlocked|Shmem:" /proc/meminfo >> $out/mem.txt; sleep 10; done ) &
 mon=$!
-ZKL_BENCH_DEVICE=0 ZKL_RCCL_LIB=$PWD/tests/stub/libnccl_shm_stub.so timeout -k 10 1100 python3 bench.py --gpus 8 --c5-log-n 18 > $out/bench_rank8.json 2> $out/bench_rank8.err
+ZKL_BENCH_DEVICE=0 ZKL_RCCL_LIB=$PWD/tests/stub/libnccl_shm_stub.so timeout -k 10 1100 python3 bench.py --full --gpus 8 --c5-log-n 18 > $out/bench_rank8.json 2> $out/bench_rank8.err
 rc=$?
 kill $mon
 echo "rc=$rc"

@@ -154,21 +154,24 @@ def test_rccl_required_with_one_gpu_per_rank(pinned):
 
 
 def test_bench_dry_run_reports_lines_and_transport_policy():
-    """--dry-run at N = 2: every rank runs the configs[4] replica line (c5_single_segment) and
+    """--full --dry-run at N = 2: every rank runs the configs[4] replica line (c5_single_segment) and
     the sharded configs[3] line; the RCCL hand-off is required with one GPU per rank and not in
     a same-device rehearsal."""
     import json
     for env, req in (({}, True), ({"ZKL_BENCH_DEVICE": "0"}, False), ({"ZKL_COMM": "gloo"}, False)):
-        r = _bench(["--gpus", "2", "--dry-run"], env)
+        r = _bench(["--gpus", "2", "--dry-run", "--full"], env)
         assert r.returncode == 0, r.stderr[-2000:]
         out = json.loads(r.stdout.strip().splitlines()[-1])
         assert out["rccl_required"] is req
         for rank in ("0", "1"):
             lines = out["lines_by_rank"][rank]
             assert "c5_single_segment" in lines and "c4_sharded" in lines and "real_program" not in lines
-    r = _bench(["--gpus", "1", "--dry-run"])
+    r = _bench(["--gpus", "1", "--dry-run", "--full"])
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["rccl_required"] is False and "real_program" in out["lines_by_rank"]["0"]
+    # a plain run is the headline alone
+    r = _bench(["--gpus", "1", "--dry-run"])
+    assert json.loads(r.stdout.strip().splitlines()[-1])["lines_by_rank"]["0"] == ["headline"]
 
 
 def test_step_chain_check_rejects_broken_chain():
@@ -240,7 +243,7 @@ def test_bench_launcher_spawns_ranks():
     (gloo rendezvous on 127.0.0.1), and rank 0's line reports n_gpus 2 with the configs[3]
     segments sharded over both ranks (--dry-run: no device work)."""
     import json
-    r = _bench(["--gpus", "2", "--dry-run", "--segments", "16"])
+    r = _bench(["--gpus", "2", "--dry-run", "--full", "--segments", "16"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout

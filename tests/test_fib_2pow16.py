@@ -27,6 +27,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 GDIR = os.path.join(ROOT, "tests", "golden")
 G = json.load(open(os.path.join(GDIR, "fib_2pow16.json")))
 SRC = "/root/reference/examples/fib-2pow16.zlisp"
+# The source is the reference's own program text, so it is not committed as a fixture: the test
+# that lowers it runs only where that tree is readable; the committed op list serves the others.
 have_ref = pytest.mark.skipif(not os.path.exists(SRC), reason="the reference tree is only in the build container")
 
 _cache = {}

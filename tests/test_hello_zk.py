@@ -62,6 +62,8 @@ def _aggregate(steps):
                              min_security_bits=c["min_security_bits"])
 
 
+# The source is the reference's own program text, so it is not committed as a fixture: this test
+# runs only where that tree is readable; the committed op list (hello_zk.json) serves the others.
 @pytest.mark.skipif(not os.path.exists(SRC), reason="the reference tree is only in the build container")
 def test_op_list_and_program_id_from_source(oracle):
     """The fixture's op list is what compile_entry lowers the file to (lower_ref restates

@@ -38,7 +38,7 @@ def test_rollup_bench_commitment_note(oracle):
     the example file in the 2025-12-26 snapshot hashes differently, so it cannot pin BLAKE3.
     Only checked when the reference tree is present (never on the GPU box)."""
     path = "/root/reference/examples/rollup-bench.zlisp"
-    if not os.path.exists(path):
+    if not os.path.exists(path):  # the reference's program text is not committed as a fixture
         pytest.skip("reference tree not present")
     src = open(path, "rb").read()
     import pyref

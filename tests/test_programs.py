@@ -31,6 +31,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 G = json.load(open(os.path.join(ROOT, "tests", "golden", "programs.json")))
 EXAMPLES = "/root/reference/examples"
+# The .zlisp sources are the reference's own program text, so they are not committed as fixtures:
+# the tests that lower them run only where that tree is readable.  Everything downstream of the
+# lowering is checked from the committed op lists (tests/golden/programs.json) everywhere.
 have_ref = pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="the reference tree is only in the build container")
 
 
