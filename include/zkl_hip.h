@@ -276,6 +276,46 @@ int zkl_hip_set_ntt_mode(int mode);
 int zkl_hip_lde(zkl_ctx* ctx, const void* d_values, uint32_t n_cols, uint32_t n_rows,
                 uint32_t blowup, void* d_coeffs_out, void* d_lde_out);
 
+/* ---- column structure (zero, constant and periodic trace columns) ----
+ * A column's row period is 0 (every row zero), a power of two P (smallest period; 1 = constant,
+ * non-zero) or ZKL_COL_GENERAL.  The prover scans each proof's trace (every row compared, periods
+ * up to 128), skips the transforms of zero columns and resumes the row hash of partitions whose
+ * leading absorb blocks hold only structured columns from a table of sponge states.  Proof bytes
+ * do not depend on it. */
+#define ZKL_COL_GENERAL 0xFFFFFFFFu
+/* Process-wide switch, default 1 (ZKL_COLSTRUCT=0 in the environment starts it at 0); 0 treats
+ * every column as general.  A proof reads it once when it starts. */
+int zkl_hip_set_column_structure(int on);
+int zkl_hip_column_structure(void);
+/* The scan on a column-major device matrix (n_rows a power of two): period_out[n_cols]. */
+int zkl_hip_scan_columns(zkl_ctx* ctx, const void* d_matrix, uint32_t n_cols, uint32_t n_rows, uint32_t* period_out);
+/* Prefix plan of the partitioned row hash of an LDE of n_lde_rows rows (host code, no device):
+ * per partition p < *n_parts_out, lead_out[p] = leading absorb blocks (10 sponge elements: the
+ * domain element, then one per folded column pair) whose columns are all structured, and
+ * q_out[p] = blowup * their largest period (1 when they are all zero or constant), the row period
+ * of the sponge state after those blocks.  lead is 0 where q would exceed n_lde_rows / 64 and for
+ * rows of more than 9 partitions.  period: per trace column, before the blowup.  lead_out and
+ * q_out have 16 entries. */
+int zkl_hip_plan_row_prefix(const uint32_t* period, uint32_t n_cols, uint64_t n_lde_rows, uint32_t blowup,
+                            uint32_t num_partitions, uint32_t hash_rate, uint32_t* lead_out, uint32_t* q_out,
+                            uint32_t* n_parts_out);
+/* zkl_hip_hash_rows with per-column row periods the caller asserts (in rows of d_matrix, natural
+ * row order); split = 1: d_matrix is an LDE in the split layout (zkl_hip_lde_columns) and the
+ * digests are written in natural row order.  The plan is zkl_hip_plan_row_prefix's with blowup 1,
+ * except that any q <= n_rows is taken (the caller asked for it; the prover's n_rows / 64 only
+ * bounds the table's cost).  *resumed_out (nullable): partitions that were resumed from the
+ * table, 0 when the dense kernels ran (switch off, nothing to skip, lane-group engine, more than
+ * 9 partitions). */
+int zkl_hip_hash_rows_periodic(zkl_ctx* ctx, const void* d_matrix, uint32_t n_cols, uint32_t n_rows,
+                               uint32_t num_partitions, uint32_t hash_rate, const uint32_t* row_period, int split,
+                               void* d_digests_out, uint32_t* resumed_out);
+/* The prover's trace LDE stage: period = NULL scans d_values, otherwise the caller's classes are
+ * taken as given; zero columns are cleared instead of transformed.  d_coeffs_out holds the
+ * prover's working form (coefficient k times 3^k at index bitrev(k)); d_lde_out is in the split
+ * layout when want_split is set and the shape supports it (*split_out says which). */
+int zkl_hip_lde_columns(zkl_ctx* ctx, const void* d_values, uint32_t n_cols, uint32_t n_rows, uint32_t blowup,
+                        const uint32_t* period, int want_split, void* d_coeffs_out, void* d_lde_out, int* split_out);
+
 /* Raw in-place radix-2 NTT on n_cols contiguous device columns of length n (stage test
  * entry point).  dif != 0: natural order in, bit-reversed out (Gentleman-Sande);
  * dif == 0: bit-reversed in, natural out (Cooley-Tukey).  inverse selects w_n^-1; no 1/n

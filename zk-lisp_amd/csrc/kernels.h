@@ -94,6 +94,49 @@ void launch_deep_coeffs(const fe* d_gam, uint32_t W, uint32_t C, const fe* d_fra
 // and write each digest to its row lde_row(q).
 void launch_hash_rows(const fe* d_mat, uint32_t n_cols, size_t n_rows, uint32_t num_partitions,
                       uint32_t hash_rate, fe* d_tmp, fe* d_out, hipStream_t s, int tag = 0, int split = 0);
+// ---- column structure (DESIGN.md §4 "Column structure") -------------------------------------
+// Row period of a column: 0 = every row zero, P = smallest power-of-two period (1 = constant,
+// non-zero), COL_GENERAL = none the scan looks for.
+constexpr uint32_t COL_GENERAL = 0xFFFFFFFFu;
+constexpr uint32_t COL_P_MAX = 128;  // largest period the scan reports
+// 0 = every column treated as general (today's dense path); default 1, ZKL_COLSTRUCT=0 or the
+// setter turn it off
+bool column_structure_enabled();
+void set_column_structure(bool on);
+// Exact scan of a column-major n_cols x n_rows matrix (n_rows a power of two), every row
+// compared: d_bits gets one word per column (zeroed, then OR-ed by the kernel), decoded on the
+// host by decode_column_scan into the period encoding above.  clear = false: the caller zeroed
+// d_bits itself (a matrix scanned in several column chunks).
+void launch_scan_columns(const fe* d_mat, uint32_t n_cols, size_t n_rows, uint32_t* d_bits, hipStream_t s,
+                         bool clear = true);
+void decode_column_scan(const uint32_t* bits, uint32_t n_cols, size_t n_rows, uint32_t* period);
+// Prefix plan of a partitioned row hash: per partition, the number of leading absorb blocks whose
+// columns are all structured (lead) and the row period q of the sponge state after them.
+struct RowPrefixPlan {
+  uint32_t np = 0;  // partitions of the row (as launch_hash_rows splits it)
+  uint32_t lead[16] = {0};
+  uint32_t q[16] = {0};  // meaningful where lead > 0
+  bool any() const {
+    for (uint32_t p = 0; p < np; p++)
+      if (lead[p]) return true;
+    return false;
+  }
+};
+// Pure host code.  period: per column as above, in rows of the matrix before the blowup (a
+// period P becomes blowup * P LDE rows; zero and constant columns stay so).  A partition's prefix
+// is used only when its q <= n_rows / rows_per_entry; rows of more than 9 partitions keep the dense path.
+// rows_per_entry: the prover's 64 keeps the table build under 1/64 of the row hash's
+// permutations; 1 (the stage entry point, periods asserted by the caller) only needs the table's
+// rows to exist.
+RowPrefixPlan plan_row_prefix(const uint32_t* period, uint32_t n_cols, size_t n_rows, uint32_t blowup,
+                              uint32_t num_partitions, uint32_t hash_rate, size_t rows_per_entry = 64);
+size_t row_prefix_table_bytes(const RowPrefixPlan& plan);
+// launch_hash_rows (tag 0) resuming the planned partitions from a prefix table built first in
+// d_table (row_prefix_table_bytes).  Falls back to launch_hash_rows (returns false) when the plan
+// is empty or the matrix-core register form would not run this shape.
+bool launch_hash_rows_prefix(const fe* d_mat, uint32_t n_cols, size_t n_rows, uint32_t num_partitions,
+                             uint32_t hash_rate, const RowPrefixPlan& plan, uint32_t* d_table, fe* d_tmp, fe* d_out,
+                             hipStream_t s, int split = 0);
 // Merkle tree: d_nodes[n..2n) must hold the leaves; fills d_nodes[1..n).
 // coin_mode (d_coin, d_root_out): the transcript step after the tree runs in the launch that
 // reaches the root -- 1: coin[0] = merge(coin[0], root) (the trace / constraint root reseed), 2:

@@ -875,6 +875,70 @@ void launch_scale_bitrev(fe* d, size_t ncols, size_t n, const fe* scale, hipStre
   scale_bitrev_kernel<<<(unsigned)((n * ncols + 255) / 256), 256, 0, s>>>(d, ncols, n, ilog2s(n), scale);
 }
 
+// ---- column scan (DESIGN.md §4 "Column structure") ------------------------------------------
+// One pass over a column-major matrix.  With R = min(COL_P_MAX, n) a column has a power-of-two
+// period <= R exactly when every row i equals row i mod R, and then its smallest period, and
+// whether it is zero, show in its first R rows alone.  Block (chunk, col) compares its chunk of
+// the column with those R rows (each thread's reference row is fixed: the chunk start and the
+// thread stride are multiples of R) and ORs into bits[col]: bit 31 = some row differs (general);
+// the chunk-0 block adds bit k = the first R rows do not have period 2^k (k < log2 R) and bit 8
+// = one of them is not zero.
+constexpr int SCAN_THREADS = 256;
+constexpr size_t SCAN_CHUNK = 4096;
+constexpr uint32_t SCAN_GENERAL = 1u << 31, SCAN_NONZERO = 1u << 8;
+static_assert(SCAN_THREADS % COL_P_MAX == 0 && SCAN_CHUNK % SCAN_THREADS == 0 && COL_P_MAX <= 128, "scan shape");
+
+__global__ __launch_bounds__(SCAN_THREADS) void scan_columns_kernel(const fe* __restrict__ M, size_t n, uint32_t R,
+                                                                   uint32_t* __restrict__ bits) {
+  const fe* col = M + (size_t)blockIdx.y * n;
+  const size_t chunk = n < SCAN_CHUNK ? n : SCAN_CHUNK, i0 = (size_t)blockIdx.x * chunk;
+  const uint32_t t = threadIdx.x;
+  const fe ref = col[t & (R - 1)];
+  uint32_t w = 0;
+  for (size_t i = t; i < chunk; i += SCAN_THREADS) {
+    const fe v = col[i0 + i];
+    if (v.lo != ref.lo || v.hi != ref.hi) w = SCAN_GENERAL;
+  }
+  if (blockIdx.x == 0 && t < R) {
+    if (ref.lo | ref.hi) w |= SCAN_NONZERO;
+    for (uint32_t k = 0; (1u << k) < R; k++)
+      if (t >= (1u << k)) {
+        const fe v = col[t - (1u << k)];
+        if (v.lo != ref.lo || v.hi != ref.hi) w |= 1u << k;
+      }
+  }
+  if (__any(w != 0)) {  // one atomic per wave that saw anything
+    for (int o = 32; o > 0; o >>= 1) w |= (uint32_t)__shfl_xor((int)w, o);
+    if ((t & 63) == 0) atomicOr(&bits[blockIdx.y], w);
+  }
+}
+
+void launch_scan_columns(const fe* d_mat, uint32_t ncols, size_t n, uint32_t* d_bits, hipStream_t s, bool clear) {
+  if (n == 0 || (n & (n - 1)) || ncols == 0 || ncols > 65535)
+    throw std::invalid_argument("launch_scan_columns: rows must be a power of two, 1..65535 columns");
+  if (clear) ZKL_HIPCHECK(hipMemsetAsync(d_bits, 0, (size_t)ncols * sizeof(uint32_t), s));
+  const uint32_t R = (uint32_t)std::min<size_t>(COL_P_MAX, n);
+  const size_t chunk = std::min(n, SCAN_CHUNK);
+  scan_columns_kernel<<<dim3((unsigned)(n / chunk), ncols), SCAN_THREADS, 0, s>>>(d_mat, n, R, d_bits);
+}
+
+void decode_column_scan(const uint32_t* bits, uint32_t ncols, size_t n, uint32_t* period) {
+  const uint32_t R = (uint32_t)std::min<size_t>(COL_P_MAX, n);
+  for (uint32_t c = 0; c < ncols; c++) {
+    const uint32_t w = bits[c];
+    uint32_t P = COL_GENERAL;
+    if (!(w & SCAN_GENERAL)) {
+      if (!(w & SCAN_NONZERO)) P = 0;
+      else {
+        P = R;  // period R holds whenever no row differs from its reference
+        for (uint32_t k = 0; (1u << k) < R; k++)
+          if (!(w & (1u << k))) { P = 1u << k; break; }
+      }
+    }
+    period[c] = P;
+  }
+}
+
 
 // =====================================================================================
 // Constraint evaluation over the CE coset (DefaultConstraintEvaluator restated):

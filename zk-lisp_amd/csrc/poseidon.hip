@@ -533,6 +533,101 @@ void launch_hash_rows(const fe* d_mat, uint32_t ncols, size_t nrows, uint32_t np
     hash_rows_kernel<0><<<pg_blocks(nrows), 256, 0, s>>>(d_mat, ncols, nrows, psize, merge, d_out, split);
 }
 
+// ---- prefix skip of the trace row hash (DESIGN.md §4 "Column structure")
+static std::atomic<int> g_colstruct{-1};
+bool column_structure_enabled() {
+  int v = g_colstruct.load();
+  if (v < 0) {
+    const char* e = getenv("ZKL_COLSTRUCT");
+    v = !(e && !strcmp(e, "0"));
+    int expect = -1;
+    if (!g_colstruct.compare_exchange_strong(expect, v)) v = expect;
+  }
+  return v != 0;
+}
+void set_column_structure(bool on) { g_colstruct.store(on ? 1 : 0); }
+
+RowPrefixPlan plan_row_prefix(const uint32_t* period, uint32_t ncols, size_t nrows, uint32_t blowup, uint32_t np,
+                              uint32_t rate, size_t rows_per_entry) {
+  RowPrefixPlan pl;
+  uint32_t psize = ncols;
+  if (np > 1) {
+    psize = (ncols + np - 1) / np;
+    if (psize < rate) psize = rate;
+  }
+  const uint32_t np_eff = (ncols + psize - 1) / psize;
+  if (np_eff > (uint32_t)PM_MAX_PARTS) return pl;
+  pl.np = np_eff;
+  if (np_eff > (uint32_t)PM_PFX_PARTS) return pl;  // merge_many over two blocks: the LDS form, dense
+  for (uint32_t p = 0; p < np_eff; p++) {
+    const uint32_t c0 = p * psize, len = std::min(psize, ncols - c0);
+    const uint32_t total = (len + 1) / 2 + 1;  // sponge elements: the domain element, then the folded pairs
+    uint32_t lead = 0;
+    uint64_t pmax = 1;
+    for (uint32_t b0 = 0; b0 < total; b0 += 10) {
+      bool ok = true;
+      uint64_t bp = 1;
+      for (uint32_t idx = std::max(b0, 1u); idx < std::min(b0 + 10, total) && ok; idx++)
+        for (uint32_t c = 2 * (idx - 1); c < std::min(2 * idx, len); c++) {
+          const uint32_t P = period[c0 + c];
+          if (P == COL_GENERAL || (P & (P - 1))) { ok = false; break; }
+          bp = std::max<uint64_t>(bp, P);
+        }
+      if (!ok) break;
+      lead++;
+      pmax = std::max(pmax, bp);
+    }
+    const uint64_t q = pmax > 1 ? pmax * blowup : 1;
+    if (lead && q <= nrows / rows_per_entry && (q & (q - 1)) == 0) {
+      pl.lead[p] = lead;
+      pl.q[p] = (uint32_t)q;
+    }
+  }
+  return pl;
+}
+
+size_t row_prefix_table_bytes(const RowPrefixPlan& pl) {
+  size_t e = 0;
+  for (uint32_t p = 0; p < pl.np; p++)
+    if (pl.lead[p]) e += pl.q[p];
+  return e * PM_PFX_ENTRY_WORDS * sizeof(uint32_t);
+}
+
+bool launch_hash_rows_prefix(const fe* d_mat, uint32_t ncols, size_t nrows, uint32_t np, uint32_t rate,
+                             const RowPrefixPlan& pl, uint32_t* d_table, fe* d_tmp, fe* d_out, hipStream_t s, int split) {
+  uint32_t psize = ncols;
+  if (np > 1) {
+    psize = (ncols + np - 1) / np;
+    if (psize < rate) psize = rate;
+  }
+  const uint32_t np_eff = (ncols + psize - 1) / psize;
+  const bool pm_rows = hash_engine() == 1 && nrows >= pm_min_items() && np_eff <= (uint32_t)PM_PFX_PARTS && !PM_ROW_BIG_CFG;
+  if (!pl.any() || !pm_rows || !d_table) {
+    launch_hash_rows(d_mat, ncols, nrows, np, rate, d_tmp, d_out, s, 0, split);
+    return false;
+  }
+  if (pl.np != np_eff) throw std::invalid_argument("launch_hash_rows_prefix: plan made for another partitioning");
+  PmRowPrefix A{};
+  A.table = d_table;
+  uint32_t off = 0;
+  size_t items = 0;
+  for (uint32_t p = 0; p < np_eff; p++) {
+    if (!pl.lead[p]) continue;
+    const uint32_t len = std::min(psize, ncols - p * psize), blocks = ((len + 1) / 2 + 1 + 9) / 10, q = pl.q[p];
+    if (pl.lead[p] > blocks || q == 0 || (q & (q - 1)) || q > nrows)
+      throw std::invalid_argument("launch_hash_rows_prefix: plan out of range");
+    A.lead[p] = pl.lead[p];
+    A.qmask[p] = q - 1;
+    A.off[p] = off;
+    off += q;
+    items += ((size_t)q + 31) / 32 * 32;
+  }
+  const uint32_t merge = row_digest_rule() == 0 ? (psize != ncols) : (np_eff > 1);
+  PM_GO(hash_rows_pm_table_kernel, items, false, s)(d_mat, ncols, nrows, psize, A, d_table, split);
+  PM_GO(hash_rows_pm_prefix_kernel, nrows, true, s)(d_mat, ncols, nrows, psize, merge, d_out, split, A);
+  return true;
+}
+
 // Tree top: several levels per launch.  Workgroup g (TOP_WAVES waves, one 48-lane state each)
 // owns nodes [cnt*g, cnt*g + cnt) of level lvl and reduces them to one node of level
 // lvl/cnt, with a workgroup barrier between levels; waves without a live node skip the

@@ -69,6 +69,7 @@ constexpr int PM_THREADS = 64 * PM_WAVES;
 constexpr int PM_ROW_WAVES = PM_ROW_WAVES_CFG;
 constexpr int PM_ROW_THREADS = 64 * PM_ROW_WAVES;
 constexpr int PM_MAX_PARTS = 16;
+constexpr int PM_PFX_PARTS = 9;  // partitions whose digests merge_many absorbs in one block (register form)
 
 // balanced base-256 digits (each in [-128, 127]) of the representative of C mod p in
 // [-128 (2^128-1)/255, 127 (2^128-1)/255]
@@ -413,10 +414,15 @@ __device__ __forceinline__ void pm_permute(const PmTables* tb, uint32_t x[6][5],
 // OUT0 = false keeps the full last round (the trace row hash's sponges: with run-time message
 // counts the state[0]-only round raised the kernel from 206 to 246 VGPRs and measured 0.7% slower;
 // the composition rows, one-block sponges, keep it: -0.7%, profiles/r06/prune/summary.md)
-template <int D, bool OUT0 = true, class Loader>
-__device__ __forceinline__ fe pm_sponge(const PmTables* tb, bool live, int nmsg, Loader ld) {
+// The sponge in two pieces, so that a caller can stop after some absorb blocks and another can
+// resume from the saved state (the row hash's prefix table, below): pm_sponge_init sets the
+// state a sponge of domain D starts from, pm_sponge_blocks absorbs and permutes the blocks whose
+// first index b0 lies in [b_from, b_to) (multiples of 10); h = (lane >> 5) & 1, the caller's.
+// pm_sponge keeps its own copy of the eight lines of pm_sponge_init: calling it there cost the row
+// kernels 40 VGPRs and a spill, and with the copy they compile to what they were.
+template <int D>
+__device__ __forceinline__ void pm_sponge_init(uint32_t x[6][5]) {
   const int h = (int)((threadIdx.x >> 5) & 1);
-  uint32_t x[6][5];
 #pragma unroll
   for (int T = 0; T < 6; T++)
 #pragma unroll
@@ -426,8 +432,13 @@ __device__ __forceinline__ fe pm_sponge(const PmTables* tb, bool live, int nmsg,
     x[0][l] = h ? 0u : c_hm.dfe130[D][l];
     x[5][l] = h ? c_hm.dom130[1][l] : c_hm.dom130[0][l];
   }
+}
+
+template <bool OUT0, class Loader>
+__device__ __forceinline__ void pm_sponge_blocks(const PmTables* tb, bool live, int nmsg, Loader ld, uint32_t x[6][5],
+                                                 int h, int b_from, int b_to) {
   const int total = nmsg + 1;
-  for (int b0 = 0; b0 < total; b0 += 10) {
+  for (int b0 = b_from; b0 < b_to; b0 += 10) {
 #pragma unroll
     for (int T = 0; T < 5; T++) {
       const int idx = b0 + 2 * T + h;
@@ -441,6 +452,22 @@ __device__ __forceinline__ fe pm_sponge(const PmTables* tb, bool live, int nmsg,
     pm_permute(tb, x, (PM_PRUNE_CFG & 1) && b0 == 0 ? pm_first_const_mask(nmsg) : 0,
                OUT0 && (PM_PRUNE_CFG & 2) && b0 + 10 >= total);
   }
+}
+
+template <int D, bool OUT0 = true, class Loader>
+__device__ __forceinline__ fe pm_sponge(const PmTables* tb, bool live, int nmsg, Loader ld) {
+  const int h = (int)((threadIdx.x >> 5) & 1);
+  uint32_t x[6][5];
+#pragma unroll
+  for (int T = 0; T < 6; T++)
+#pragma unroll
+    for (int l = 0; l < 5; l++) x[T][l] = 0;
+#pragma unroll
+  for (int l = 0; l < 5; l++) {
+    x[0][l] = h ? 0u : c_hm.dfe130[D][l];
+    x[5][l] = h ? c_hm.dom130[1][l] : c_hm.dom130[0][l];
+  }
+  pm_sponge_blocks<OUT0>(tb, live, nmsg, ld, x, h, 0, nmsg + 1);
   return from_mont130(x[0]);
 }
 
@@ -694,6 +721,19 @@ __device__ __forceinline__ fe pm_from_low_half(fe v) {
   return fe{(uint64_t)w0 | ((uint64_t)w1 << 32), (uint64_t)w2 | ((uint64_t)w3 << 32)};
 }
 
+// Prefix skip (DESIGN.md §4 "Column structure"): when the columns feeding the first lead[p]
+// absorb blocks of partition p are all zero, constant or periodic in the row, the sponge state
+// after those blocks depends only on (row mod Q[p]), Q[p] a power of two.  hash_rows_pm_table_kernel
+// computes that state once per residue (table entry = the 12 state elements as 5 Montgomery limbs
+// each, [q][element][limb]); hash_rows_pm_prefix_kernel loads it and resumes at block lead[p].
+struct PmRowPrefix {
+  const uint32_t* table;
+  uint32_t lead[PM_PFX_PARTS];   // leading absorb blocks taken from the table (0: none)
+  uint32_t qmask[PM_PFX_PARTS];  // Q[p] - 1
+  uint32_t off[PM_PFX_PARTS];    // first table entry of partition p
+};
+constexpr int PM_PFX_ENTRY_WORDS = 60;
+
 template <int TAG, bool BIG>
 __global__ __launch_bounds__(PM_ROW_THREADS) void hash_rows_pm_kernel(const fe* __restrict__ M, uint32_t ncols,
                                                                  size_t nrows, uint32_t psize, uint32_t merge,
@@ -750,6 +790,112 @@ __global__ __launch_bounds__(PM_ROW_THREADS) void hash_rows_pm_kernel(const fe* 
       }
     }
     if (live && pm_h == 0) out[lde_row(row, nrows, split)] = d;
+  }
+}
+
+// hash_rows_pm_kernel<0, false> (the trace rows, at most PM_PFX_PARTS partitions, their digests in
+// registers) with the partitions the plan names resumed from the prefix table; the others, and
+// merge_many, run as there
+__global__ __launch_bounds__(PM_ROW_THREADS) void hash_rows_pm_prefix_kernel(const fe* __restrict__ M, uint32_t ncols,
+                                                                        size_t nrows, uint32_t psize, uint32_t merge,
+                                                                        fe* __restrict__ out, int split, PmRowPrefix A) {
+  __shared__ PmTables tb;
+  pm_load_tables(&tb);
+  const uint32_t np = (ncols + psize - 1) / psize;
+  PM_LOOP(nrows) {
+    const int n = pm_lane & 31;
+    const size_t row0 = pm_b * 32 + (size_t)n;
+    const bool live = row0 < nrows;
+    const size_t row = live ? row0 : 0;
+    fe d = fe_zero();
+    fe msg[5] = {fe_zero(), fe_zero(), fe_zero(), fe_zero(), fe_zero()};
+    for (uint32_t p = 0; p < np; p++) {
+      const uint32_t c0 = p * psize;
+      const uint32_t len = min(psize, ncols - c0);
+      const fe* base = M + (size_t)c0 * nrows + row;  // position (split: the row is lde_row)
+      const int nmsg = (int)((len + 1) / 2);
+      const uint32_t lead = A.lead[p];  // wave-uniform
+      uint32_t x[6][5];
+      if (lead) {
+        const size_t q = lde_row(row, nrows, split) & (size_t)A.qmask[p];
+        const uint32_t* e = A.table + ((size_t)A.off[p] + q) * PM_PFX_ENTRY_WORDS + pm_h * 5;
+#pragma unroll
+        for (int T = 0; T < 6; T++)
+#pragma unroll
+          for (int l = 0; l < 5; l++) x[T][l] = e[T * 10 + l];
+      } else {
+        pm_sponge_init<DOM_ELEMS>(x);
+      }
+      // first-block pruning applies only to a sponge that starts at block 0 (pm_sponge_blocks)
+      pm_sponge_blocks<false>(&tb, live, nmsg, [&](int j) {
+        fe a = base[(size_t)(2 * j) * nrows];
+        fe b = (2u * j + 1 < len) ? base[(size_t)(2 * j + 1) * nrows] : fe_zero();
+        return fold_pair(a, b);
+      }, x, pm_h, 10 * (int)lead, nmsg + 1);
+      d = from_mont130(x[0]);
+      if (merge) {
+        const fe v = pm_from_low_half(d);
+        const int slot = (int)(p + 1) >> 1;
+        if ((int)((p + 1) & 1) == pm_h) {
+#pragma unroll
+          for (int t = 0; t < 5; t++)
+            if (t == slot) msg[t] = v;
+        }
+      }
+    }
+    if (merge) {
+      d = pm_sponge<DOM_MANY, false>(&tb, live, (int)np, [&](int i) {
+        const int slot = (i + 1) >> 1;
+        fe r = msg[0];
+#pragma unroll
+        for (int t = 1; t < 5; t++)
+          if (t == slot) r = msg[t];
+        return r;
+      });
+    }
+    if (live && pm_h == 0) out[lde_row(row, nrows, split)] = d;
+  }
+}
+
+// Prefix table of the kernel above: for every partition p with lead[p] > 0 and every natural row
+// q < Q[p] (stored at position lde_pos(q)), the sponge state after lead[p] absorb blocks, by the
+// row kernel's own sponge code.  Partition p owns ceil(Q[p] / 32) batches of 32 rows.
+__global__ __launch_bounds__(PM_THREADS) void hash_rows_pm_table_kernel(const fe* __restrict__ M, uint32_t ncols,
+                                                                       size_t nrows, uint32_t psize, PmRowPrefix A,
+                                                                       uint32_t* __restrict__ table, int split) {
+  __shared__ PmTables tb;
+  pm_load_tables(&tb);
+  const uint32_t np = (ncols + psize - 1) / psize;
+  size_t batches = 0;
+  for (uint32_t p = 0; p < np; p++) batches += A.lead[p] ? ((size_t)A.qmask[p] + 32) >> 5 : 0;
+  PM_LOOP(batches * 32) {
+    size_t b = pm_b;
+    uint32_t p = 0;
+    for (; p + 1 < np; p++) {
+      const size_t nb = A.lead[p] ? ((size_t)A.qmask[p] + 32) >> 5 : 0;
+      if (b < nb) break;
+      b -= nb;
+    }
+    const size_t q0 = b * 32 + (size_t)(pm_lane & 31);
+    const bool live = q0 <= (size_t)A.qmask[p];
+    const size_t q = live ? q0 : 0;
+    const uint32_t c0 = p * psize;
+    const uint32_t len = min(psize, ncols - c0);
+    const fe* base = M + (size_t)c0 * nrows + lde_pos(q, nrows, split);
+    uint32_t x[6][5];
+    pm_sponge_init<DOM_ELEMS>(x);
+    pm_sponge_blocks<false>(&tb, live, (int)((len + 1) / 2), [&](int j) {
+      fe a = base[(size_t)(2 * j) * nrows];
+      fe b2 = (2u * j + 1 < len) ? base[(size_t)(2 * j + 1) * nrows] : fe_zero();
+      return fold_pair(a, b2);
+    }, x, pm_h, 0, 10 * (int)A.lead[p]);
+    if (live) {
+      uint32_t* e = table + ((size_t)A.off[p] + q) * PM_PFX_ENTRY_WORDS + pm_h * 5;
+#pragma unroll
+      for (int T = 0; T < 6; T++)
+#pragma unroll
+        for (int l = 0; l < 5; l++) e[T * 10 + l] = x[T][l];
+    }
   }
 }
 

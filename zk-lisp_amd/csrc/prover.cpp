@@ -127,6 +127,13 @@ struct zkl_ctx {
   DBuf cexinv;  // 1 / (x - g^(n-1)) over the CE coset: shape-only, kept while the key matches
   size_t cexinv_key_n = 0, cexinv_key_ce = 0, cexinv_key_tab = 0;
   const void* cexinv_key_roots = nullptr;
+  // column structure: scan words, the row hash's prefix table, and which column
+  // slices of coef / lde this context itself left all-zero (valid for the buffers and shape in
+  // zero_key; every writer of the two buffers is in prove_impl and updates it)
+  DBuf scanbits, pfxtab;
+  HBuf h_scan;
+  std::vector<uint8_t> zero_known;
+  struct { const void* coef = nullptr; const void* lde = nullptr; size_t n = 0, N = 0, W = 0; } zero_key;
   DBuf kconst;  // ProofConsts of the proof in flight on this context (written by copies only)
   DBuf dconst;  // DerivedConsts: what the device derives per proof (pose_k, DEEP coefficients)
   DBuf fri_coin;  // device transcript of the FRI layers: seed, alpha, layer roots
@@ -494,30 +501,96 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   // src: the caller's resident trace, read by the iNTT's first pass (nullptr: already in coef)
   auto lde_cols = [&](uint32_t c0, uint32_t nc, const fe* src) {
     fe* cf = C->coef.f() + (size_t)c0 * n;
-    launch_intt_scaled(src, cf, nc, n, miroots, Ntab, C->opow_n.f(), s);
+    launch_intt_scaled(src ? src + (size_t)c0 * n : nullptr, cf, nc, n, miroots, Ntab, C->opow_n.f(), s);
     const int sp = launch_lde_from_coeffs(cf, nc, n, N, mroots, Ntab, C->lde.f() + (size_t)c0 * N, s, g_lde_split);
     // the row hash, evaluator and DEEP read every column with one layout (the NTT mode cannot
     // change during a proof: zkl_hip_set_ntt_mode refuses while one is in flight)
     if (split >= 0 && sp != split) throw std::runtime_error("internal: trace LDE chunks in different layouts");
     split = sp;
   };
+  // Column structure: the scan classes every column of this proof's trace (nothing is kept from
+  // an earlier proof's trace); zero columns skip the transforms, and the row hash resumes the
+  // partitions whose leading absorb blocks are structured from a table.  A host trace is scanned
+  // chunk by chunk behind its upload and keeps the dense LDE (its chunks are queued before any
+  // class could come back without stalling the upload); only its row hash uses the classes.
+  const bool colstruct = column_structure_enabled();
+  const bool zkey_ok = C->zero_key.coef == C->coef.p && C->zero_key.lde == C->lde.p && C->zero_key.n == n &&
+                       C->zero_key.N == N && C->zero_key.W == W && C->zero_known.size() == W;
+  if (!zkey_ok) C->zero_known.assign(W, 0);
+  C->zero_key.coef = nullptr;  // invalid while this proof queues its writes
+  std::vector<uint32_t> period;
+  uint32_t* hbits = nullptr;
+  if (colstruct) {
+    C->scanbits.ensure((size_t)W * sizeof(uint32_t));
+    C->h_scan.ensure((size_t)W * sizeof(uint32_t));
+    hbits = C->h_scan.at<uint32_t>();
+  }
+  auto read_scan = [&] {
+    HIPCHECK(hipMemcpyAsync(hbits, C->scanbits.p, (size_t)W * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    period.resize(W);
+    decode_column_scan(hbits, W, n, period.data());
+  };
   if (trace_on_host) {
     KScope k(C, KF_NTT);
-    upload_trace_chunked(C, d_trace_in, W, n, s, [&](uint32_t c0, uint32_t nc) { lde_cols(c0, nc, nullptr); });
-  } else {
+    std::fill(C->zero_known.begin(), C->zero_known.end(), 0);  // the upload writes every coef column
+    if (colstruct) HIPCHECK(hipMemsetAsync(C->scanbits.p, 0, (size_t)W * sizeof(uint32_t), s));
+    upload_trace_chunked(C, d_trace_in, W, n, s, [&](uint32_t c0, uint32_t nc) {
+      if (colstruct) launch_scan_columns(C->coef.f() + (size_t)c0 * n, nc, n, (uint32_t*)C->scanbits.p + c0, s, false);
+      lde_cols(c0, nc, nullptr);
+    });
+  } else if (!colstruct) {
     C->up_ms = 0;
     KScope k(C, KF_NTT);
+    std::fill(C->zero_known.begin(), C->zero_known.end(), 0);
     lde_cols(0, W, (const fe*)d_trace_in);
+  } else {
+    C->up_ms = 0;
+    {
+      KScope k(C, KF_MISC);
+      launch_scan_columns((const fe*)d_trace_in, W, n, (uint32_t*)C->scanbits.p, s);
+      check_launch("column scan");
+      read_scan();
+    }
+    KScope k(C, KF_NTT);
+    // runs of zero columns: their coef / lde slices are cleared unless this context left them
+    // zero already; runs of the others go through the transforms
+    for (uint32_t c0 = 0; c0 < W;) {
+      uint32_t c1 = c0;
+      const bool zero = period[c0] == 0;
+      while (c1 < W && (period[c1] == 0) == zero) c1++;
+      if (!zero) {
+        lde_cols(c0, c1 - c0, (const fe*)d_trace_in);
+        std::fill(C->zero_known.begin() + c0, C->zero_known.begin() + c1, 0);
+      } else {
+        for (uint32_t a = c0; a < c1;) {  // sub-runs not known to be zero
+          if (C->zero_known[a]) { a++; continue; }
+          uint32_t b = a;
+          while (b < c1 && !C->zero_known[b]) b++;
+          HIPCHECK(hipMemsetAsync(C->coef.f() + (size_t)a * n, 0, (size_t)(b - a) * n * sizeof(fe), s));
+          HIPCHECK(hipMemsetAsync(C->lde.f() + (size_t)a * N, 0, (size_t)(b - a) * N * sizeof(fe), s));
+          std::fill(C->zero_known.begin() + a, C->zero_known.begin() + b, 1);
+          a = b;
+        }
+      }
+      c0 = c1;
+    }
   }
   check_launch("trace LDE");
   if (split < 0) split = 0;
+  C->zero_key.coef = C->coef.p; C->zero_key.lde = C->lde.p; C->zero_key.n = n; C->zero_key.N = N; C->zero_key.W = W;
   T.mark(1);
   // ---- trace commitment (commit_to_rows + MerkleTree)
   C->parts.ensure((size_t)o.num_partitions * N * sizeof(fe) + N * sizeof(fe));
   C->tree.ensure(2 * N * sizeof(fe));
+  if (colstruct && trace_on_host) read_scan();
   {
+    RowPrefixPlan plan;
+    if (colstruct) plan = plan_row_prefix(period.data(), W, N, B, o.num_partitions, o.hash_rate);
+    if (plan.any()) C->pfxtab.ensure(row_prefix_table_bytes(plan));
     KScope k(C, KF_TRACE_HASH);
-    launch_hash_rows(C->lde.f(), W, N, o.num_partitions, o.hash_rate, C->parts.f(), C->tree.f() + N, s, 0, split);
+    launch_hash_rows_prefix(C->lde.f(), W, N, o.num_partitions, o.hash_rate, plan, (uint32_t*)C->pfxtab.p, C->parts.f(),
+                            C->tree.f() + N, s, split);
   }
   check_launch("trace row hash");
   // ---- coin seed: Context::to_elements || AirPublicInputs::to_elements (agg/fs.rs:67-73),
@@ -1435,6 +1508,116 @@ int zkl_hip_hash_rows(zkl_ctx* c, const void* d_m, uint32_t nc, uint32_t nr, uin
     launch_hash_rows((const fe*)d_m, nc, nr, np, rate, c->parts.f(), (fe*)d_out, c->stream);
     check_launch("stage entry point");
     HIPCHECK(hipStreamSynchronize(c->stream));
+  });
+}
+
+int zkl_hip_set_column_structure(int on) {
+  if (on < 0 || on > 1) return ZKL_E_INVALID;
+  set_column_structure(on != 0);
+  return 0;
+}
+
+int zkl_hip_column_structure(void) { return column_structure_enabled() ? 1 : 0; }
+
+int zkl_hip_scan_columns(zkl_ctx* c, const void* d_m, uint32_t nc, uint32_t nr, uint32_t* period_out) {
+  if (!c || !d_m || !period_out || nc == 0 || nc > 4096 || nr == 0 || (nr & (nr - 1))) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    c->scanbits.ensure((size_t)nc * sizeof(uint32_t));
+    c->h_scan.ensure((size_t)nc * sizeof(uint32_t));
+    launch_scan_columns((const fe*)d_m, nc, nr, (uint32_t*)c->scanbits.p, c->stream);
+    check_launch("stage entry point");
+    HIPCHECK(hipMemcpyAsync(c->h_scan.p, c->scanbits.p, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    decode_column_scan(c->h_scan.at<uint32_t>(), nc, nr, period_out);
+  });
+}
+
+int zkl_hip_plan_row_prefix(const uint32_t* period, uint32_t nc, uint64_t n_lde_rows, uint32_t blowup, uint32_t np,
+                            uint32_t rate, uint32_t* lead_out, uint32_t* q_out, uint32_t* n_parts_out) {
+  if (!period || !lead_out || !q_out || nc == 0 || np < 1 || np > 16 || rate < 1 || rate > 256 || blowup < 1 ||
+      (blowup & (blowup - 1)))
+    return ZKL_E_INVALID;
+  return run_guarded(nullptr, [&] {
+    const RowPrefixPlan pl = plan_row_prefix(period, nc, (size_t)n_lde_rows, blowup, np, rate);
+    for (int p = 0; p < 16; p++) {
+      lead_out[p] = pl.lead[p];
+      q_out[p] = pl.lead[p] ? pl.q[p] : 0;
+    }
+    if (n_parts_out) *n_parts_out = pl.np;
+  });
+}
+
+int zkl_hip_hash_rows_periodic(zkl_ctx* c, const void* d_m, uint32_t nc, uint32_t nr, uint32_t np, uint32_t rate,
+                               const uint32_t* row_period, int split, void* d_out, uint32_t* resumed_out) {
+  if (resumed_out) *resumed_out = 0;
+  if (!c || !d_m || !d_out || !row_period || nc == 0 || np < 1 || np > 16 || rate < 1 || rate > 256 || split < 0 ||
+      split > 1 || (split && (nr < 2048 || (nr & (nr - 1)))))
+    return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    upload_hasher(c->stream);
+    c->parts.ensure((size_t)std::max<uint32_t>(np, 1) * nr * sizeof(fe) + 16);
+    RowPrefixPlan plan;
+    if (column_structure_enabled()) plan = plan_row_prefix(row_period, nc, nr, 1, np, rate, 1);
+    if (plan.any()) c->pfxtab.ensure(row_prefix_table_bytes(plan));
+    const bool used = launch_hash_rows_prefix((const fe*)d_m, nc, nr, np, rate, plan, (uint32_t*)c->pfxtab.p,
+                                              c->parts.f(), (fe*)d_out, c->stream, split);
+    if (used && resumed_out)
+      for (uint32_t p = 0; p < plan.np; p++) *resumed_out += plan.lead[p] != 0;
+    check_launch("stage entry point");
+    HIPCHECK(hipStreamSynchronize(c->stream));
+  });
+}
+
+int zkl_hip_lde_columns(zkl_ctx* c, const void* d_values, uint32_t nc, uint32_t n, uint32_t blowup,
+                        const uint32_t* period, int want_split, void* d_coeffs, void* d_lde, int* split_out) {
+  if (!c || !d_values || !d_coeffs || !d_lde || nc == 0 || nc > 4096 || n < 2 || (n & (n - 1)) || blowup < 2 ||
+      (blowup & (blowup - 1)))
+    return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    const size_t N = (size_t)n * blowup;
+    ensure_tables(c, n, N);
+    hipStream_t s = c->stream;
+    std::vector<uint32_t> per(nc, COL_GENERAL);
+    if (column_structure_enabled()) {
+      if (period) {
+        per.assign(period, period + nc);
+      } else {
+        c->scanbits.ensure((size_t)nc * sizeof(uint32_t));
+        c->h_scan.ensure((size_t)nc * sizeof(uint32_t));
+        launch_scan_columns((const fe*)d_values, nc, n, (uint32_t*)c->scanbits.p, s);
+        HIPCHECK(hipMemcpyAsync(c->h_scan.p, c->scanbits.p, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        decode_column_scan(c->h_scan.at<uint32_t>(), nc, n, per.data());
+      }
+    }
+    const MontTab mi = mont_tab(c->miroots.p, c->tab_N), mr = mont_tab(c->mroots.p, c->tab_N);
+    int split = -1;
+    for (uint32_t c0 = 0; c0 < nc;) {
+      uint32_t c1 = c0;
+      const bool zero = per[c0] == 0;
+      while (c1 < nc && (per[c1] == 0) == zero) c1++;
+      fe* cf = (fe*)d_coeffs + (size_t)c0 * n;
+      fe* out = (fe*)d_lde + (size_t)c0 * N;
+      if (zero) {
+        HIPCHECK(hipMemsetAsync(cf, 0, (size_t)(c1 - c0) * n * sizeof(fe), s));
+        HIPCHECK(hipMemsetAsync(out, 0, (size_t)(c1 - c0) * N * sizeof(fe), s));
+      } else {
+        launch_intt_scaled((const fe*)d_values + (size_t)c0 * n, cf, c1 - c0, n, mi, c->tab_N, c->opow_n.f(), s);
+        const int sp = launch_lde_from_coeffs(cf, c1 - c0, n, N, mr, c->tab_N, out, s, want_split != 0);
+        if (split >= 0 && sp != split) throw std::runtime_error("internal: LDE column runs in different layouts");
+        split = sp;
+      }
+      c0 = c1;
+    }
+    check_launch("stage entry point");
+    HIPCHECK(hipStreamSynchronize(s));
+    if (split_out) *split_out = split < 0 ? 0 : split;
   });
 }
 

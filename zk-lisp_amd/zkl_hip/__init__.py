@@ -157,6 +157,15 @@ def load_library():
     lib.zkl_step_proof_digest.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.zkl_children_root.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p]
     lib.zkl_hip_lde.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.zkl_hip_set_column_structure.argtypes = [C.c_int]
+    lib.zkl_hip_column_structure.argtypes = []
+    lib.zkl_hip_scan_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(C.c_uint32)]
+    lib.zkl_hip_plan_row_prefix.argtypes = [P(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
+    lib.zkl_hip_hash_rows_periodic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               P(C.c_uint32), C.c_int, C.c_void_p, P(C.c_uint32)]
+    lib.zkl_hip_lde_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32),
+                                        C.c_int, C.c_void_p, C.c_void_p, P(C.c_int)]
     lib.zkl_synth_vm_segment_chain.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P(F128), C.c_void_p,
                                                P(AirPublicInputs), P(C.c_uint32)]
     lib.zkl_build_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p,
@@ -388,6 +397,43 @@ class row_digest_rule:
     def __exit__(self, *exc):
         load_library().zkl_hip_set_row_digest_rule(self.prev)
         return False
+
+
+COL_GENERAL = 0xFFFFFFFF  # row period of a column with no structure (ZKL_COL_GENERAL)
+
+
+class column_structure:
+    """Context manager: the process-wide column-structure switch (zkl_hip_set_column_structure)
+    for the duration of the block."""
+
+    def __init__(self, on: bool):
+        self.on = 1 if on else 0
+
+    def __enter__(self):
+        lib = load_library()
+        self.prev = lib.zkl_hip_column_structure()
+        if lib.zkl_hip_set_column_structure(self.on) != 0:
+            raise ZklError(-1, "zkl_hip_set_column_structure failed")
+        return self
+
+    def __exit__(self, *exc):
+        load_library().zkl_hip_set_column_structure(self.prev)
+        return False
+
+
+def plan_row_prefix(periods, n_lde_rows: int, blowup: int, num_partitions: int, hash_rate: int = 16):
+    """Host planning of the row hash's prefix skip: periods per trace column (0 zero, a power of
+    two, COL_GENERAL).  Returns (lead, q), one entry per partition of the row; q is None where
+    lead is 0."""
+    lib = load_library()
+    per = (C.c_uint32 * len(periods))(*[int(x) for x in periods])
+    lead, q, np_ = (C.c_uint32 * 16)(), (C.c_uint32 * 16)(), C.c_uint32(0)
+    rc = lib.zkl_hip_plan_row_prefix(per, len(periods), n_lde_rows, blowup, num_partitions, hash_rate, lead, q,
+                                     C.byref(np_))
+    if rc != 0:
+        raise ZklError(rc, "zkl_hip_plan_row_prefix: invalid arguments")
+    k = np_.value
+    return tuple(lead[:k]), tuple(q[p] if lead[p] else None for p in range(k))
 
 
 def device_count() -> int:
@@ -710,6 +756,37 @@ class Context:
                                         C.c_void_p(d_out))
         if rc:
             self._err(rc)
+
+    def scan_columns(self, d_mat, n_cols, n_rows):
+        """Row period per column of a column-major device matrix (0, a power of two <= 128, or
+        COL_GENERAL); every row is compared."""
+        out = (C.c_uint32 * n_cols)()
+        rc = self.lib.zkl_hip_scan_columns(self.ptr, C.c_void_p(d_mat), n_cols, n_rows, out)
+        if rc != 0:
+            raise ZklError(rc, self._err(rc))
+        return list(out)
+
+    def hash_rows_periodic(self, d_mat, n_cols, n_rows, num_partitions, hash_rate, row_periods, d_out, split=0):
+        """zkl_hip_hash_rows with caller-asserted row periods; returns how many partitions were
+        resumed from the prefix table (0: the dense kernels ran)."""
+        per = (C.c_uint32 * n_cols)(*[int(x) for x in row_periods])
+        used = C.c_uint32(0)
+        rc = self.lib.zkl_hip_hash_rows_periodic(self.ptr, C.c_void_p(d_mat), n_cols, n_rows, num_partitions,
+                                                 hash_rate, per, split, C.c_void_p(d_out), C.byref(used))
+        if rc != 0:
+            raise ZklError(rc, self._err(rc))
+        return used.value
+
+    def lde_columns(self, d_values, n_cols, n_rows, blowup, d_coeffs, d_lde, periods=None, want_split=False) -> int:
+        """The prover's trace LDE stage (zero columns cleared, not transformed); returns 1 when
+        d_lde is in the split layout."""
+        per = None if periods is None else (C.c_uint32 * n_cols)(*[int(x) for x in periods])
+        sp = C.c_int(0)
+        rc = self.lib.zkl_hip_lde_columns(self.ptr, C.c_void_p(d_values), n_cols, n_rows, blowup, per,
+                                          1 if want_split else 0, C.c_void_p(d_coeffs), C.c_void_p(d_lde), C.byref(sp))
+        if rc != 0:
+            raise ZklError(rc, self._err(rc))
+        return sp.value
 
     def set_kernel_timing(self, mode: int):
         """0: no kernel-family events, 1: trace row hash only (default), 2: every family."""
