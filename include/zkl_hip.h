@@ -310,9 +310,16 @@ int zkl_hip_hash_rows_periodic(zkl_ctx* ctx, const void* d_matrix, uint32_t n_co
                                uint32_t num_partitions, uint32_t hash_rate, const uint32_t* row_period, int split,
                                void* d_digests_out, uint32_t* resumed_out);
 /* The prover's trace LDE stage: period = NULL scans d_values, otherwise the caller's classes are
- * taken as given; zero columns are cleared instead of transformed.  d_coeffs_out holds the
+ * taken as given; this is the routine the prover runs.  Zero columns are cleared instead of
+ * transformed, columns of a power-of-two period below n_rows get a small LDE tiled over the
+ * column, the others go through the transforms in one launch group.  d_coeffs_out holds the
  * prover's working form (coefficient k times 3^k at index bitrev(k)); d_lde_out is in the split
- * layout when want_split is set and the shape supports it (*split_out says which). */
+ * layout when want_split is set and the shape supports it (*split_out says which).
+ * The context remembers which slices of this (d_coeffs_out, d_lde_out) pair its last call left
+ * zero and does not clear them again while the pair, n_cols, n_rows and blowup stay the same.  A
+ * write into either buffer through this context's other entry points is noticed; a caller that
+ * writes them by other means (its own kernels, another context) must use another pair for the
+ * next call or run that call with the switch off. */
 int zkl_hip_lde_columns(zkl_ctx* ctx, const void* d_values, uint32_t n_cols, uint32_t n_rows, uint32_t blowup,
                         const uint32_t* period, int want_split, void* d_coeffs_out, void* d_lde_out, int* split_out);
 

@@ -186,10 +186,27 @@ void launch_ntt_stages(fe* d_data, size_t n_cols, size_t N, bool dif, int lo_log
 // supports it; returns 1 when the output is split, 0 when it is in natural order.
 // all stages of a DIF iNTT of n-element columns (natural in, bit-reversed out), reading src
 // (nullptr: in place in d) and storing element i of each column times scale[bitrev(i)]
+// d_cmap (both calls): a device array of n_cols column indices; kernel column k then addresses
+// column d_cmap[k] of d_src, d_data, d_coef and d_out, so columns scattered over a matrix go
+// through one launch group (nullptr: columns 0..n_cols).  n_cols = 0 launches nothing;
+// launch_lde_from_coeffs still returns the layout it would store.
 void launch_intt_scaled(const fe* d_src, fe* d_data, size_t n_cols, size_t n, MontTab iroots, size_t Ntab,
-                        const fe* d_scale, hipStream_t s);
+                        const fe* d_scale, hipStream_t s, const uint32_t* d_cmap = nullptr);
 int launch_lde_from_coeffs(const fe* d_coef, size_t n_cols, size_t n, size_t N, MontTab roots, size_t Ntab, fe* d_out,
-                           hipStream_t s, bool want_split = false);
+                           hipStream_t s, bool want_split = false, const uint32_t* d_cmap = nullptr);
+// Periodic columns (period P, a power of two <= COL_P_MAX and below n) of the column-major n-row
+// matrix d_src, listed in d_cols: the B P-point coset LDE of each (B = N / n) goes to d_small[y *
+// small_stride ..] in natural row order, and the first min(COL_P_MAX, n) entries of its d_coef
+// column are written (the P scaled coefficients in the dense layout, zero after them; the caller
+// keeps the rest of the column zero).  d_roots / d_iroots: canonical tables w^i, w^-i of Ntab >= N
+// entries, d_opow: 3^k for k < n.
+void launch_periodic_lde(const fe* d_src, size_t n, size_t N, const uint32_t* d_cols, uint32_t n_cols, uint32_t P,
+                         const fe* d_roots, const fe* d_iroots, size_t Ntab, const fe* d_opow, fe* d_coef,
+                         fe* d_small, size_t small_stride, hipStream_t s);
+// LDE column d_cols[y] := its small LDE of d_bp[y] = B P rows repeated, in natural order or the
+// split layout (lde_pos below)
+void launch_periodic_tile(const fe* d_small, size_t small_stride, const uint32_t* d_cols, const uint32_t* d_bp,
+                          uint32_t n_cols, size_t N, int split, fe* d_lde, hipStream_t s);
 // Even/odd split layout of a trace LDE column.  Write the N = 256 S rows as
 // r = L + t S (L < S, t < 256); the last DIT pass owns, per block, 8 consecutive L (L0 + l)
 // and all t, and must store in place, so the layout permutes within that set: row (L, t) goes
@@ -270,12 +287,16 @@ struct OodArgs {
   const fe* pw2;
   uint32_t ncols, chunks, use_off;
   uint32_t off[16];
+  const uint32_t* zero;  // nullable, per column: non-zero = every coefficient is zero, write 0 unread
 };
 void launch_ood(const OodArgs& a, fe* d_partial, hipStream_t s);
 // The OOD frame from the two launch_ood partial sets: chunk sums, composition columns scaled by
 // mult[j]; written in transcript order t(z) [W] | H(z) [C] | t(zg) [W] | H(zg) [C].
 void launch_ood_frame(const fe* d_partial_trace, const fe* d_partial_comp, uint32_t W, uint32_t C, uint32_t chunks,
                       const fe* mult /* C host values */, fe* d_frame, hipStream_t s);
+// d_list (launch_deep, nullable): the n_list columns to sum instead of all W + C, as indices into
+// the coefficient order (trace column c, composition column W + j); the columns left out must be
+// all-zero trace columns.
 struct DeepParams {  // the frame dot products come from DerivedConsts::deep_sz (launch_deep_coeffs)
   size_t N;
   uint32_t W, C;
@@ -285,7 +306,7 @@ struct DeepParams {  // the frame dot products come from DerivedConsts::deep_sz 
 void launch_deep_denoms(const fe* d_roots, size_t Ntab, size_t N, fe z, fe zg, fe* d_dinv, hipStream_t s);
 void launch_deep(const fe* d_lde, const fe* d_clde, const fe* d_roots, size_t Ntab, const DeepParams& p,
                  const DerivedConsts* dD, const fe* d_dinv /* from launch_deep_denoms */, fe* d_out, hipStream_t s,
-                 int split = 0);
+                 int split = 0, const uint32_t* d_list = nullptr, uint32_t n_list = 0);
 void launch_fri_leaves(const fe* d_ev, size_t Nd, fe* d_leaves, hipStream_t s);
 // alpha read from device memory (coin[1], written by the layer tree's launch_merkle)
 void launch_fri_fold(const fe* d_ev, size_t Nd, const fe* d_alpha, const fe* d_iroots, size_t Ntab, fe* d_out,

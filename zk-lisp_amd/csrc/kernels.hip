@@ -128,10 +128,13 @@ void build_mont_table(const fe* w, size_t N, void* d_buf, hipStream_t s) {
 // blowup copies of the (scaled, bit-reversed) coefficients are generated on load rather than
 // materialised.  scale != nullptr (last DIF pass): element i of a column is stored multiplied by
 // scale[bitrev(i)] (the coefficient scaling of an iNTT whose output is bit-reversed).
+// cmap != nullptr (the trace LDE's general columns): kernel column k addresses
+// column cmap[k] of data and src; nullptr keeps k itself (a wave-uniform select).
 template <bool DIF>
 __global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(fe* __restrict__ data, size_t ncols, int logN, int r,
                                                        int logS, MontTab roots, int logTab, const fe* __restrict__ src,
-                                                       int src_logb, const fe* __restrict__ scale = nullptr) {
+                                                       int src_logb, const fe* __restrict__ scale = nullptr,
+                                                       const uint32_t* __restrict__ cmap = nullptr) {
   __shared__ fe buf[NTT_ELEMS + NTT_ELEMS / 16];
   const int R = 1 << r;
   const int G = NTT_ELEMS >> r;
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(fe* __restrict__ 
   const bool whole = gpc >= (size_t)G;
   if (whole) {
     col_fixed = blockIdx.x % (unsigned)ncols;
+    if (cmap) col_fixed = cmap[col_fixed];
     qbase = (size_t)(blockIdx.x / (unsigned)ncols) * G;
   }
   auto locate = [&](int g, size_t& col, size_t& q) -> bool {
@@ -157,7 +161,9 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(fe* __restrict__ 
     const size_t qg = (size_t)blockIdx.x * G + g;
     col = qg >> log_gpc;
     q = qg & (gpc - 1);
-    return col < ncols;
+    if (col >= ncols) return false;
+    if (cmap) col = cmap[col];
+    return true;
   };
   auto addr = [&](int g, int t, bool& ok) -> size_t {
     size_t col, q;
@@ -254,7 +260,7 @@ __device__ __forceinline__ fe ntt_canon(const uint32_t l[5]) {
 template <int ELEMS, int THREADS>
 __global__ __launch_bounds__(THREADS) void ntt_dit_lazy_kernel(fe* __restrict__ data, size_t ncols, int logN, int r,
                                                                   int logS, MontTab roots, const fe* __restrict__ src,
-                                                                  int src_logb) {
+                                                                  int src_logb, const uint32_t* __restrict__ cmap) {
   constexpr int PITCHED = ELEMS + ELEMS / 16;
   __shared__ uint4 bufA[PITCHED];     // limbs 0..3 (16-byte accesses, as the canonical kernel)
   __shared__ uint32_t bufB[PITCHED];  // limb 4
@@ -269,6 +275,7 @@ __global__ __launch_bounds__(THREADS) void ntt_dit_lazy_kernel(fe* __restrict__ 
   const bool whole = gpc >= (size_t)G;
   if (whole) {
     col_fixed = blockIdx.x % (unsigned)ncols;
+    if (cmap) col_fixed = cmap[col_fixed];
     qbase = (size_t)(blockIdx.x / (unsigned)ncols) * G;
   }
   auto locate = [&](int g, size_t& col, size_t& q) -> bool {
@@ -280,7 +287,9 @@ __global__ __launch_bounds__(THREADS) void ntt_dit_lazy_kernel(fe* __restrict__ 
     const size_t qg = (size_t)blockIdx.x * G + g;
     col = qg >> log_gpc;
     q = qg & (gpc - 1);
-    return col < ncols;
+    if (col >= ncols) return false;
+    if (cmap) col = cmap[col];
+    return true;
   };
   auto addr = [&](int g, int t, bool& ok) -> size_t {
     size_t col, q;
@@ -396,7 +405,8 @@ __global__ __launch_bounds__(THREADS) void ntt_dit_lazy_kernel(fe* __restrict__ 
 template <int ELEMS, int THREADS>
 __global__ __launch_bounds__(THREADS) void ntt_ct_lazy_kernel(fe* __restrict__ data, size_t ncols, int logN, int r,
                                                                  int logS, MontTab roots, const fe* __restrict__ src,
-                                                                 int src_logb, const fe* __restrict__ scale) {
+                                                                 int src_logb, const fe* __restrict__ scale,
+                                                                 const uint32_t* __restrict__ cmap) {
   constexpr int PITCHED = ELEMS + ELEMS / 16;
   __shared__ uint4 bufA[PITCHED];
   __shared__ uint32_t bufB[PITCHED];
@@ -411,6 +421,7 @@ __global__ __launch_bounds__(THREADS) void ntt_ct_lazy_kernel(fe* __restrict__ d
   const bool whole = gpc >= (size_t)G;
   if (whole) {
     col_fixed = blockIdx.x % (unsigned)ncols;
+    if (cmap) col_fixed = cmap[col_fixed];
     qbase = (size_t)(blockIdx.x / (unsigned)ncols) * G;
   }
   auto locate = [&](int g, size_t& col, size_t& q) -> bool {
@@ -422,7 +433,9 @@ __global__ __launch_bounds__(THREADS) void ntt_ct_lazy_kernel(fe* __restrict__ d
     const size_t qg = (size_t)blockIdx.x * G + g;
     col = qg >> log_gpc;
     q = qg & (gpc - 1);
-    return col < ncols;
+    if (col >= ncols) return false;
+    if (cmap) col = cmap[col];
+    return true;
   };
   auto addr = [&](int g, int t, bool& ok) -> size_t {
     size_t col, q;
@@ -542,7 +555,8 @@ constexpr int NTT8_THREADS = 256;
 constexpr int NTT8_PITCH = 257;
 __global__ __launch_bounds__(NTT8_THREADS) __global__ __launch_bounds__(NTT8_THREADS) void ntt_dit8_kernel(fe* __restrict__ data, size_t ncols, int logN, int logS,
                                                                  MontTab roots, const fe* __restrict__ src, int src_logb,
-                                                                 int lfast, int split) {
+                                                                 int lfast, int split,
+                                                                 const uint32_t* __restrict__ cmap) {
   __shared__ uint4 bufA[NTT8_G * NTT8_PITCH];
   __shared__ uint32_t bufB[NTT8_G * NTT8_PITCH];
   const int tid = (int)threadIdx.x;
@@ -560,6 +574,7 @@ __global__ __launch_bounds__(NTT8_THREADS) __global__ __launch_bounds__(NTT8_THR
     col = blockIdx.x % (unsigned)ncols;
     q = (size_t)(blockIdx.x / (unsigned)ncols) * NTT8_G + g;
   }
+  if (cmap) col = cmap[col];
   const size_t S = (size_t)1 << logS;
   const size_t L = q & (S - 1), Hb = q >> logS;
   const size_t base = (col << logN) + ((Hb << logS) << 8) + L;
@@ -756,9 +771,10 @@ static bool dit_split_ok(size_t N, int lo, int hi) {
 
 // DIF: src (out of place) feeds the first pass, scale the last pass's stores (see ntt_pass_kernel)
 static void ntt_passes(fe* d, size_t ncols, size_t N, bool dif, int lo, int hi, MontTab roots, size_t Ntab,
-                       const fe* src, int src_logb, hipStream_t s, int split = 0, const fe* scale = nullptr) {
+                       const fe* src, int src_logb, hipStream_t s, int split = 0, const fe* scale = nullptr,
+                       const uint32_t* cmap = nullptr) {
   int logN = ilog2s(N), logTab = ilog2s(Ntab);
-  if (hi < lo) return;
+  if (hi < lo || ncols == 0) return;
   const std::vector<int> rs = ntt_split(hi - lo + 1);
   if (dif) {
     int cur = hi;
@@ -776,14 +792,14 @@ static void ntt_passes(fe* d, size_t ncols, size_t N, bool dif, int lo, int hi, 
         const size_t Gw = wide ? 2 * G : G;
         const unsigned grid = (unsigned)((groups + Gw - 1) / Gw);
         if (wide && wm == 2)
-          ntt_ct_lazy_kernel<2 * NTT_ELEMS, 2 * NTT_THREADS><<<grid, 2 * NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots, sp, 0, sc);
+          ntt_ct_lazy_kernel<2 * NTT_ELEMS, 2 * NTT_THREADS><<<grid, 2 * NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots, sp, 0, sc, cmap);
         else if (wide)
-          ntt_ct_lazy_kernel<2 * NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots, sp, 0, sc);
+          ntt_ct_lazy_kernel<2 * NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots, sp, 0, sc, cmap);
         else
-          ntt_ct_lazy_kernel<NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots, sp, 0, sc);
+          ntt_ct_lazy_kernel<NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots, sp, 0, sc, cmap);
       } else {
         ntt_pass_kernel<true><<<(unsigned)((groups + G - 1) / G), NTT_THREADS, 0, s>>>(d, ncols, logN, r, logS, roots,
-                                                                                      logTab, sp, 0, sc);
+                                                                                      logTab, sp, 0, sc, cmap);
       }
       cur -= r;
     }
@@ -804,16 +820,16 @@ static void ntt_passes(fe* d, size_t ncols, size_t N, bool dif, int lo, int hi, 
         const fe* sp = cur == lo ? src : nullptr;
         if (r == 8 && ntt8_enabled() && ((size_t)1 << cur) >= (size_t)NTT8_G && (N >> 8) >= (size_t)NTT8_G)
           ntt_dit8_kernel<<<(unsigned)(groups / NTT8_G), NTT8_THREADS, 0, s>>>(d, ncols, logN, cur, roots, sp, src_logb,
-                                                                              ntt8_lfast(cur), split_here);
+                                                                              ntt8_lfast(cur), split_here, cmap);
         else if (wide && wm == 2)
-          ntt_dit_lazy_kernel<2 * NTT_ELEMS, 2 * NTT_THREADS><<<grid, 2 * NTT_THREADS, 0, s>>>(d, ncols, logN, r, cur, roots, sp, src_logb);
+          ntt_dit_lazy_kernel<2 * NTT_ELEMS, 2 * NTT_THREADS><<<grid, 2 * NTT_THREADS, 0, s>>>(d, ncols, logN, r, cur, roots, sp, src_logb, cmap);
         else if (wide)
-          ntt_dit_lazy_kernel<2 * NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, cur, roots, sp, src_logb);
+          ntt_dit_lazy_kernel<2 * NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, cur, roots, sp, src_logb, cmap);
         else
-          ntt_dit_lazy_kernel<NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, cur, roots, sp, src_logb);
+          ntt_dit_lazy_kernel<NTT_ELEMS, NTT_THREADS><<<grid, NTT_THREADS, 0, s>>>(d, ncols, logN, r, cur, roots, sp, src_logb, cmap);
       } else
         ntt_pass_kernel<false><<<(unsigned)((groups + G - 1) / G), NTT_THREADS, 0, s>>>(
-            d, ncols, logN, r, cur, roots, logTab, cur == lo ? src : nullptr, src_logb);
+            d, ncols, logN, r, cur, roots, logTab, cur == lo ? src : nullptr, src_logb, nullptr, cmap);
       cur += r;
     }
   }
@@ -825,22 +841,24 @@ void launch_ntt_stages(fe* d, size_t ncols, size_t N, bool dif, int lo, int hi, 
 }
 
 void launch_intt_scaled(const fe* src, fe* d, size_t ncols, size_t n, MontTab iroots, size_t Ntab, const fe* scale,
-                        hipStream_t s) {
+                        hipStream_t s, const uint32_t* d_cmap) {
   const int logn = ilog2s(n);
   if (logn == 0) throw std::invalid_argument("launch_intt_scaled: n must be at least 2");
-  ntt_passes(d, ncols, n, true, 0, logn - 1, iroots, Ntab, src, 0, s, 0, scale);
+  ntt_passes(d, ncols, n, true, 0, logn - 1, iroots, Ntab, src, 0, s, 0, scale, d_cmap);
 }
 
 int launch_lde_from_coeffs(const fe* d_coef, size_t ncols, size_t n, size_t N, MontTab roots, size_t Ntab, fe* d_out,
-                           hipStream_t s, bool want_split) {
+                           hipStream_t s, bool want_split, const uint32_t* d_cmap) {
   const int logB = ilog2s(N / n);
   if (logB == 0) {
+    if (d_cmap) throw std::invalid_argument("launch_lde_from_coeffs: a column map needs a blowup of at least 2");
+    if (ncols == 0) return 0;
     ZKL_HIPCHECK(hipMemcpyAsync(d_out, d_coef, ncols * n * sizeof(fe), hipMemcpyDeviceToDevice, s));
     ntt_passes(d_out, ncols, N, false, 0, ilog2s(N) - 1, roots, Ntab, nullptr, 0, s);
     return 0;
   }
   const int split = want_split && dit_split_ok(N, logB, ilog2s(N) - 1) ? 1 : 0;
-  ntt_passes(d_out, ncols, N, false, logB, ilog2s(N) - 1, roots, Ntab, d_coef, logB, s, split);
+  ntt_passes(d_out, ncols, N, false, logB, ilog2s(N) - 1, roots, Ntab, d_coef, logB, s, split, nullptr, d_cmap);
   return split;
 }
 
@@ -937,6 +955,103 @@ void decode_column_scan(const uint32_t* bits, uint32_t ncols, size_t n, uint32_t
     }
     period[c] = P;
   }
+}
+
+// ---- periodic columns (DESIGN.md §4 "Column structure") -------------------------------------
+// A column with v[i] = v[i mod P] (P a power of two below n) interpolates to f(x) = h(x^(n/P)),
+// h the interpolant of v[0..P) over <g^(n/P)>.  Its scaled coefficients c_k 3^k are non-zero only
+// at k = j n/P, which the bit-reversed coef layout puts at position bitrev_P(j) < P, and natural
+// LDE row r is sum_j (h_j 3^(j n/P)) w_(BP)^(r j): row r mod BP of a BP-point transform.  Both
+// sums are evaluated directly (P <= 128 terms, exact field arithmetic, so the canonical bytes are
+// those of the full transform).  Block (chunk, y) takes column cols[y]: every block redoes the
+// P-point interpolation in LDS, then writes PER_ROWS of the BP small-LDE rows to small[y *
+// small_stride + r]; the chunk-0 block also writes the column's first `head` coefficients (zero
+// beyond P).  Both sums are split over min(256 / P, P) resp. min(4, P) threads per output and
+// added through LDS (field addition is exact, so the split does not show in the result): the
+// twiddle loads of a single 128-term chain per thread left the launch latency-bound.
+constexpr int PER_THREADS = 256, PER_EPARTS = 4, PER_ROWS = PER_THREADS / PER_EPARTS;
+__global__ __launch_bounds__(PER_THREADS) void periodic_lde_kernel(
+    const fe* __restrict__ src, size_t n, const uint32_t* __restrict__ cols, uint32_t logP, uint32_t logBP,
+    const fe* __restrict__ roots, const fe* __restrict__ iroots, int logTab, const fe* __restrict__ opow, fe invP,
+    uint32_t head, fe* __restrict__ coef, fe* __restrict__ small, size_t small_stride) {
+  __shared__ fe v[COL_P_MAX], c[COL_P_MAX], red[PER_THREADS];
+  const uint32_t P = 1u << logP, BP = 1u << logBP, t = threadIdx.x;
+  const size_t col = cols[blockIdx.y];
+  if (t < P) v[t] = src[col * n + t];
+  __syncthreads();
+  {  // h_j = 1/P sum_i v_i w_P^(-i j): thread (part, j) sums the terms i of its part
+    const uint32_t parts = min((uint32_t)PER_THREADS >> logP, P), len = P / parts;  // powers of two
+    const uint32_t j = t & (P - 1), part = t >> logP;
+    fe acc = fe_zero();
+    if (part < parts) {
+#pragma unroll 4
+      for (uint32_t i = part * len; i < (part + 1) * len; i++)
+        acc = fe_add(acc, fe_mul(v[i], iroots[(size_t)((i * j) & (P - 1)) << (logTab - logP)]));
+    }
+    red[t] = acc;  // part * P + j
+    __syncthreads();
+    if (t < P) {
+      for (uint32_t k = 1; k < parts; k++) acc = fe_add(acc, red[k * P + t]);
+      c[t] = fe_mul(fe_mul(acc, invP), opow[(size_t)t * (n >> logP)]);
+    }
+    __syncthreads();
+  }
+  if (blockIdx.x == 0 && t < head) {
+    fe* cf = coef + col * n;
+    if (t < P) cf[bitrev(t, (int)logP)] = c[t];
+    else cf[t] = fe_zero();
+  }
+  // row r = sum_j c_j w_BP^(r j): thread (part, row) sums the terms j of its part
+  const uint32_t eparts = min((uint32_t)PER_EPARTS, P), elen = P / eparts;
+  const uint32_t rl = t & (PER_ROWS - 1), epart = t / PER_ROWS;
+  const uint32_t r = blockIdx.x * PER_ROWS + rl;
+  fe acc = fe_zero();
+  if (r < BP && epart < eparts) {
+#pragma unroll 4
+    for (uint32_t j = epart * elen; j < (epart + 1) * elen; j++)
+      acc = fe_add(acc, fe_mul(c[j], roots[(size_t)((r * j) & (BP - 1)) << (logTab - logBP)]));
+  }
+  red[t] = acc;  // epart * PER_ROWS + rl
+  __syncthreads();
+  if (t < PER_ROWS && r < BP) {
+    for (uint32_t k = 1; k < eparts; k++) acc = fe_add(acc, red[k * PER_ROWS + t]);
+    small[blockIdx.y * small_stride + r] = acc;
+  }
+}
+
+// lde[col][pos] = small[y][lde_row(pos) mod B P(y)] for every position of column cols[y]
+__global__ __launch_bounds__(256) void periodic_tile_kernel(const fe* __restrict__ small, size_t small_stride,
+                                                            const uint32_t* __restrict__ cols,
+                                                            const uint32_t* __restrict__ bp, size_t N, int split,
+                                                            fe* __restrict__ lde) {
+  const fe* sm = small + blockIdx.y * small_stride;
+  const size_t mask = (size_t)bp[blockIdx.y] - 1;
+  fe* out = lde + (size_t)cols[blockIdx.y] * N;
+  for (size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pos < N; pos += (size_t)gridDim.x * blockDim.x)
+    out[pos] = sm[lde_row(pos, N, split) & mask];
+}
+
+void launch_periodic_lde(const fe* d_src, size_t n, size_t N, const uint32_t* d_cols, uint32_t ncols, uint32_t P,
+                         const fe* d_roots, const fe* d_iroots, size_t Ntab, const fe* d_opow, fe* d_coef,
+                         fe* d_small, size_t small_stride, hipStream_t s) {
+  if (ncols == 0) return;
+  const size_t B = N / n;
+  if (P == 0 || (P & (P - 1)) || P > COL_P_MAX || P >= n || B * P > small_stride || B * P > Ntab || ncols > 65535)
+    throw std::invalid_argument("launch_periodic_lde: period must be a power of two <= 128 and below n");
+  const uint32_t BP = (uint32_t)(B * P), head = (uint32_t)std::min<size_t>(COL_P_MAX, n);
+  static_assert(COL_P_MAX <= PER_THREADS, "one thread per coefficient of the head");
+  periodic_lde_kernel<<<dim3((BP + PER_ROWS - 1) / PER_ROWS, ncols), PER_THREADS, 0, s>>>(
+      d_src, n, d_cols, (uint32_t)ilog2s(P), (uint32_t)ilog2s(BP), d_roots, d_iroots, ilog2s(Ntab), d_opow,
+      fe_inv(fe{P, 0}), head, d_coef, d_small, small_stride);
+}
+
+void launch_periodic_tile(const fe* d_small, size_t small_stride, const uint32_t* d_cols, const uint32_t* d_bp,
+                          uint32_t ncols, size_t N, int split, fe* d_lde, hipStream_t s) {
+  if (ncols == 0) return;
+  if (ncols > 65535) throw std::invalid_argument("launch_periodic_tile: at most 65535 columns");
+  // 16 elements per thread: ~9500 blocks for the 37 periodic columns of the headline trace
+  const unsigned gx = (unsigned)std::max<size_t>(1, N / (256 * 16));
+  periodic_tile_kernel<<<dim3(gx, ncols), 256, 0, s>>>(d_small, small_stride, d_cols, d_bp, N, split, d_lde);
 }
 
 
@@ -1158,6 +1273,10 @@ void launch_check_zero_range_bitrev(const fe* d, size_t N, size_t lo, size_t hi,
 // per point read every coefficient twice, 445 MB per launch for 214 MB of coefficients).
 __global__ __launch_bounds__(256) void ood_kernel(OodArgs A, fe* partial) {
   const uint32_t c = blockIdx.x, k = blockIdx.z;
+  if (A.zero && A.zero[c]) {  // an all-zero column (its coefficients are zero): both sums are zero
+    if (threadIdx.x < 2) partial[((size_t)threadIdx.x * A.ncols + c) * A.chunks + k] = fe_zero();
+    return;
+  }
   const fe* col = A.coef + (A.use_off ? (size_t)A.off[c] : (size_t)c * A.col_stride);
   const size_t len = A.n / A.chunks, j0 = (size_t)k * len;
   uint32_t acc1[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, acc2[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1216,7 +1335,8 @@ __device__ __forceinline__ fe limbs_canon(const uint32_t l[5]) {
 __global__ __launch_bounds__(256) void deep_kernel(const fe* __restrict__ lde, const fe* __restrict__ clde,
                                                    const fe* __restrict__ roots, int shift, DeepParams p,
                                                    const DerivedConsts* __restrict__ K, const fe* __restrict__ dinv,
-                                                   fe* out, int split) {
+                                                   fe* out, int split, const uint32_t* __restrict__ list,
+                                                   uint32_t nlist) {
   const size_t T = (size_t)gridDim.x * blockDim.x;
   const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t col[DEEP_PTS][10];
@@ -1224,24 +1344,27 @@ __global__ __launch_bounds__(256) void deep_kernel(const fe* __restrict__ lde, c
   for (int k = 0; k < DEEP_PTS; k++)
 #pragma unroll
     for (int u = 0; u < 10; u++) col[k][u] = 0;
-  const uint32_t ncol = p.W + p.C;
+  // list: the columns to sum, this proof's non-zero trace columns and then the
+  // composition columns W..W+C-1; a zero column only ever added g * 0.  nullptr: all W + C.
+  const uint32_t ncol = list ? nlist : p.W + p.C;
   for (uint32_t c0 = 0; c0 < ncol; c0 += DEEP_COLS) {
     fe v[DEEP_COLS][DEEP_PTS];
 #pragma unroll
     for (int cc = 0; cc < DEEP_COLS; cc++) {
-      const uint32_t c = c0 + cc;
+      const uint32_t e = min(c0 + cc, ncol - 1);
+      const uint32_t c = list ? list[e] : e;
       // thread point k is LDE position q = i0 + k T (whole lines of the trace columns, which may
       // be in the split layout), i.e. row lde_row(q); composition columns are in natural order
       const bool tr = c < p.W;
       const fe* src = tr ? lde + (size_t)c * p.N : clde + (size_t)(c - p.W) * p.N;
 #pragma unroll
       for (int k = 0; k < DEEP_PTS; k++)
-        v[cc][k] = c < ncol ? src[tr ? i0 + k * T : lde_row(i0 + k * T, p.N, split)] : fe_zero();
+        v[cc][k] = c0 + cc < ncol ? src[tr ? i0 + k * T : lde_row(i0 + k * T, p.N, split)] : fe_zero();
     }
 #pragma unroll
     for (int cc = 0; cc < DEEP_COLS; cc++) {
-      const uint32_t c = min(c0 + cc, ncol - 1);  // a padded column contributes g * 0
-      const uint32_t* g = K->deep_m[c];
+      const uint32_t e = min(c0 + cc, ncol - 1);  // a padded column contributes g * 0
+      const uint32_t* g = K->deep_m[list ? list[e] : e];
       const uint32_t gm[5] = {g[0], g[1], g[2], g[3], g[4]};
 #pragma unroll
       for (int k = 0; k < DEEP_PTS; k++) {
@@ -1331,11 +1454,13 @@ void launch_deep_denoms(const fe* d_roots, size_t Ntab, size_t N, fe z, fe zg, f
 }
 
 void launch_deep(const fe* d_lde, const fe* d_clde, const fe* d_roots, size_t Ntab, const DeepParams& p,
-                 const DerivedConsts* dK, const fe* d_dinv, fe* d_out, hipStream_t s, int split) {
+                 const DerivedConsts* dK, const fe* d_dinv, fe* d_out, hipStream_t s, int split,
+                 const uint32_t* d_list, uint32_t n_list) {
+  if (d_list && (n_list == 0 || n_list > p.W + p.C)) throw std::invalid_argument("launch_deep: bad column list");
   // N is a power of two >= 64: every thread gets exactly DEEP_PTS points
   const size_t threads = std::min<size_t>(256, p.N / DEEP_PTS);
   deep_kernel<<<(unsigned)(p.N / (threads * DEEP_PTS)), (unsigned)threads, 0, s>>>(
-      d_lde, d_clde, d_roots, ilog2s(Ntab) - ilog2s(p.N), p, dK, d_dinv, d_out, split);
+      d_lde, d_clde, d_roots, ilog2s(Ntab) - ilog2s(p.N), p, dK, d_dinv, d_out, split, d_list, n_list);
 }
 
 // fold: (v0+v1)/2 + alpha (v0-v1) / (2 x0), x0 = GENERATOR * g_d^i (constant offset, agg/trace.rs:764-800)

@@ -25,6 +25,7 @@
 #include "air_host.h"
 #include "host_hash.h"
 #include "kernels.h"
+#include "lde_plan.h"
 #include "host_proof.h"
 #include "proof_view.h"
 
@@ -40,6 +41,8 @@ void children_root(const uint8_t suite[32], const uint8_t* digests, const uint8_
 namespace {
 
 #define HIPCHECK(x) ZKL_HIPCHECK(x)
+
+static_assert(LDE_COL_GENERAL == COL_GENERAL && LDE_P_MAX == COL_P_MAX, "lde_plan.h restates kernels.h");
 
 struct InvalidArg : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -127,13 +130,15 @@ struct zkl_ctx {
   DBuf cexinv;  // 1 / (x - g^(n-1)) over the CE coset: shape-only, kept while the key matches
   size_t cexinv_key_n = 0, cexinv_key_ce = 0, cexinv_key_tab = 0;
   const void* cexinv_key_roots = nullptr;
-  // column structure: scan words, the row hash's prefix table, and which column
-  // slices of coef / lde this context itself left all-zero (valid for the buffers and shape in
-  // zero_key; every writer of the two buffers is in prove_impl and updates it)
-  DBuf scanbits, pfxtab;
-  HBuf h_scan;
-  std::vector<uint8_t> zero_known;
-  struct { const void* coef = nullptr; const void* lde = nullptr; size_t n = 0, N = 0, W = 0; } zero_key;
+  // column structure: scan words, the row hash's prefix table, the per-proof
+  // column lists (colmeta, uploaded from h_meta), the small LDEs of the periodic columns, and
+  // which column slices of coef / lde this context itself left zero: zero_known for the prover's
+  // own buffers (every writer of the two is in prove_impl and updates it), zero_stage for the
+  // caller's buffers of zkl_hip_lde_columns (every entry point that can write caller memory
+  // forgets it)
+  DBuf scanbits, pfxtab, colmeta, psmall;
+  HBuf h_scan, h_meta;
+  ZeroBook zero_known, zero_stage;
   DBuf kconst;  // ProofConsts of the proof in flight on this context (written by copies only)
   DBuf dconst;  // DerivedConsts: what the device derives per proof (pose_k, DEEP coefficients)
   DBuf fri_coin;  // device transcript of the FRI layers: seed, alpha, layer roots
@@ -468,6 +473,90 @@ struct InFlight {
   ~InFlight() { g_proofs_in_flight.fetch_sub(1); }
 };
 
+// Per-call column lists in device memory, built from the scan's periods: one
+// pinned-to-device copy of 5 W + 16 words.
+struct ColMeta {
+  const uint32_t* zero = nullptr;     // [W] 1 = all-zero column (ood_kernel)
+  const uint32_t* general = nullptr;  // column map of the trace LDE's one launch group
+  const uint32_t* pcols = nullptr;    // periodic columns, grouped by period
+  const uint32_t* pbp = nullptr;      // rows B * P of their small LDEs
+  const uint32_t* deep = nullptr;     // the non-zero trace columns, then W .. W + 15 (deep_kernel)
+  uint32_t n_nonzero = 0;
+};
+
+ColMeta upload_col_meta(zkl_ctx* C, const LdePlan& pl, uint32_t W, uint32_t B, hipStream_t s) {
+  const size_t words = 5 * (size_t)W + 16;
+  C->colmeta.ensure(words * sizeof(uint32_t));
+  C->h_meta.ensure(words * sizeof(uint32_t));
+  uint32_t* h = C->h_meta.at<uint32_t>();  // the last call that read it has synchronised
+  memset(h, 0, words * sizeof(uint32_t));
+  for (uint32_t c = 0; c < W; c++) h[c] = pl.zero[c];
+  std::copy(pl.general.begin(), pl.general.end(), h + W);
+  std::copy(pl.pcols.begin(), pl.pcols.end(), h + 2 * (size_t)W);
+  for (size_t k = 0; k < pl.pper.size(); k++) h[3 * (size_t)W + k] = pl.pper[k] * B;
+  std::copy(pl.nonzero.begin(), pl.nonzero.end(), h + 4 * (size_t)W);
+  for (uint32_t j = 0; j < 16; j++) h[4 * (size_t)W + pl.nonzero.size() + j] = W + j;
+  HIPCHECK(hipMemcpyAsync(C->colmeta.p, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  const uint32_t* d = (const uint32_t*)C->colmeta.p;
+  ColMeta m;
+  m.zero = d; m.general = d + W; m.pcols = d + 2 * (size_t)W; m.pbp = d + 3 * (size_t)W; m.deep = d + 4 * (size_t)W;
+  m.n_nonzero = (uint32_t)pl.nonzero.size();
+  return m;
+}
+
+// The trace LDE of a device-resident matrix (DefaultTraceLde::new), shared by prove_impl and
+// zkl_hip_lde_columns.  period == nullptr: every column through iNTT -> n*coef bit-reversed,
+// scale c_k * 3^k (coset shift), DIT, and the book forgets every column.  Otherwise (column
+// structure): the general columns take those transforms in one launch group
+// through a column map, wherever they sit; a periodic column gets its B P-point LDE tiled over
+// the column and its P coefficients; a zero column is cleared unless the book knows this context
+// left it zero.  `book` covers the (coef, lde) pair and is updated for what is queued here;
+// *meta_out gets the device lists for the later readers.  Returns the layout of every LDE
+// column (1 = split).
+int trace_lde_columns(zkl_ctx* C, ZeroBook& book, const fe* d_src, uint32_t W, size_t n, size_t N,
+                      const uint32_t* period, fe* coef, fe* lde, bool want_split, ColMeta* meta_out, hipStream_t s) {
+  const MontTab mi = mont_tab(C->miroots.p, C->tab_N), mr = mont_tab(C->mroots.p, C->tab_N);
+  const size_t Ntab = C->tab_N;
+  book.begin(coef, lde, n, N, W);
+  int split;
+  if (!period) {
+    book.all_unknown();
+    launch_intt_scaled(d_src, coef, W, n, mi, Ntab, C->opow_n.f(), s);
+    split = launch_lde_from_coeffs(coef, W, n, N, mr, Ntab, lde, s, want_split);
+  } else {
+    const uint32_t B = (uint32_t)(N / n);
+    const LdePlan pl = plan_structured_lde(period, W, n, book);
+    const ColMeta m = upload_col_meta(C, pl, W, B, s);
+    if (meta_out) *meta_out = m;
+    const size_t head = std::min<size_t>(LDE_P_MAX, n);
+    for (auto& r : pl.clear_all) {
+      HIPCHECK(hipMemsetAsync(coef + (size_t)r.first * n, 0, (size_t)(r.second - r.first) * n * sizeof(fe), s));
+      HIPCHECK(hipMemsetAsync(lde + (size_t)r.first * N, 0, (size_t)(r.second - r.first) * N * sizeof(fe), s));
+    }
+    for (auto& r : pl.clear_tail)
+      for (uint32_t c = r.first; c < r.second; c++)  // the heads in between are written below
+        HIPCHECK(hipMemsetAsync(coef + (size_t)c * n + head, 0, (n - head) * sizeof(fe), s));
+    const uint32_t ng = (uint32_t)pl.general.size(), npc = (uint32_t)pl.pcols.size();
+    launch_intt_scaled(d_src, coef, ng, n, mi, Ntab, C->opow_n.f(), s, m.general);
+    // with no general column this still reports the layout the later readers expect
+    split = launch_lde_from_coeffs(coef, ng, n, N, mr, Ntab, lde, s, want_split, m.general);
+    if (npc) {
+      const size_t stride = (size_t)B * LDE_P_MAX;
+      C->psmall.ensure((size_t)npc * stride * sizeof(fe));
+      for (uint32_t a = 0; a < npc;) {  // one small-LDE launch per period present
+        uint32_t b = a;
+        while (b < npc && pl.pper[b] == pl.pper[a]) b++;
+        launch_periodic_lde(d_src, n, N, m.pcols + a, b - a, pl.pper[a], C->roots.f(), C->iroots.f(), Ntab,
+                            C->opow.f(), coef, C->psmall.f() + (size_t)a * stride, stride, s);
+        a = b;
+      }
+      launch_periodic_tile(C->psmall.f(), stride, m.pcols, m.pbp, npc, N, split, lde, s);
+    }
+  }
+  book.commit(coef, lde, n, N, W);
+  return split;
+}
+
 // the proof bytes are left in C->proof_s (zkl_hip_last_proof), valid until the next proof
 void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t W, uint32_t n32,
                 const zkl_air_public_inputs& pi, const zkl_proof_options& o) {
@@ -514,10 +603,8 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   // chunk by chunk behind its upload and keeps the dense LDE (its chunks are queued before any
   // class could come back without stalling the upload); only its row hash uses the classes.
   const bool colstruct = column_structure_enabled();
-  const bool zkey_ok = C->zero_key.coef == C->coef.p && C->zero_key.lde == C->lde.p && C->zero_key.n == n &&
-                       C->zero_key.N == N && C->zero_key.W == W && C->zero_known.size() == W;
-  if (!zkey_ok) C->zero_known.assign(W, 0);
-  C->zero_key.coef = nullptr;  // invalid while this proof queues its writes
+  ZeroBook& book = C->zero_known;
+  ColMeta meta;  // null lists: the later readers walk every column
   std::vector<uint32_t> period;
   uint32_t* hbits = nullptr;
   if (colstruct) {
@@ -533,57 +620,38 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   };
   if (trace_on_host) {
     KScope k(C, KF_NTT);
-    std::fill(C->zero_known.begin(), C->zero_known.end(), 0);  // the upload writes every coef column
+    book.begin(C->coef.p, C->lde.p, n, N, W);
+    book.all_unknown();  // the upload writes every coef column
     if (colstruct) HIPCHECK(hipMemsetAsync(C->scanbits.p, 0, (size_t)W * sizeof(uint32_t), s));
     upload_trace_chunked(C, d_trace_in, W, n, s, [&](uint32_t c0, uint32_t nc) {
       if (colstruct) launch_scan_columns(C->coef.f() + (size_t)c0 * n, nc, n, (uint32_t*)C->scanbits.p + c0, s, false);
       lde_cols(c0, nc, nullptr);
     });
-  } else if (!colstruct) {
-    C->up_ms = 0;
-    KScope k(C, KF_NTT);
-    std::fill(C->zero_known.begin(), C->zero_known.end(), 0);
-    lde_cols(0, W, (const fe*)d_trace_in);
+    book.commit(C->coef.p, C->lde.p, n, N, W);
   } else {
     C->up_ms = 0;
-    {
+    if (colstruct) {
       KScope k(C, KF_MISC);
       launch_scan_columns((const fe*)d_trace_in, W, n, (uint32_t*)C->scanbits.p, s);
       check_launch("column scan");
       read_scan();
     }
     KScope k(C, KF_NTT);
-    // runs of zero columns: their coef / lde slices are cleared unless this context left them
-    // zero already; runs of the others go through the transforms
-    for (uint32_t c0 = 0; c0 < W;) {
-      uint32_t c1 = c0;
-      const bool zero = period[c0] == 0;
-      while (c1 < W && (period[c1] == 0) == zero) c1++;
-      if (!zero) {
-        lde_cols(c0, c1 - c0, (const fe*)d_trace_in);
-        std::fill(C->zero_known.begin() + c0, C->zero_known.begin() + c1, 0);
-      } else {
-        for (uint32_t a = c0; a < c1;) {  // sub-runs not known to be zero
-          if (C->zero_known[a]) { a++; continue; }
-          uint32_t b = a;
-          while (b < c1 && !C->zero_known[b]) b++;
-          HIPCHECK(hipMemsetAsync(C->coef.f() + (size_t)a * n, 0, (size_t)(b - a) * n * sizeof(fe), s));
-          HIPCHECK(hipMemsetAsync(C->lde.f() + (size_t)a * N, 0, (size_t)(b - a) * N * sizeof(fe), s));
-          std::fill(C->zero_known.begin() + a, C->zero_known.begin() + b, 1);
-          a = b;
-        }
-      }
-      c0 = c1;
-    }
+    split = trace_lde_columns(C, book, (const fe*)d_trace_in, W, n, N, colstruct ? period.data() : nullptr, C->coef.f(),
+                              C->lde.f(), g_lde_split, &meta, s);
   }
   check_launch("trace LDE");
   if (split < 0) split = 0;
-  C->zero_key.coef = C->coef.p; C->zero_key.lde = C->lde.p; C->zero_key.n = n; C->zero_key.N = N; C->zero_key.W = W;
   T.mark(1);
   // ---- trace commitment (commit_to_rows + MerkleTree)
   C->parts.ensure((size_t)o.num_partitions * N * sizeof(fe) + N * sizeof(fe));
   C->tree.ensure(2 * N * sizeof(fe));
-  if (colstruct && trace_on_host) read_scan();
+  if (colstruct && trace_on_host) {
+    // the dense LDE wrote exact zeros for the zero columns: DEEP and OOD get the lists here too
+    read_scan();
+    ZeroBook none;
+    meta = upload_col_meta(C, plan_structured_lde(period.data(), W, n, none), W, B, s);
+  }
   {
     RowPrefixPlan plan;
     if (colstruct) plan = plan_row_prefix(period.data(), W, N, B, o.num_partitions, o.hash_rate);
@@ -812,6 +880,7 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
     OodArgs a{};
     a.coef = C->coef.f(); a.col_stride = n; a.elem_stride = 1; a.n = n;
     a.pw1 = pw + 2 * n; a.pw2 = pw + 3 * n; a.ncols = W; a.chunks = chunks; a.use_off = 0;
+    a.zero = meta.zero;
     launch_ood(a, dood, s);
     OodArgs b{};
     b.coef = C->ce.f(); b.col_stride = 0; b.elem_stride = ce / n; b.n = n;
@@ -862,7 +931,9 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   C->deep.ensure(N * sizeof(fe));
   {
     KScope k(C, KF_DEEP);
-    launch_deep(C->lde.f(), C->clde.f(), roots, Ntab, dp, dD, C->xinv.f(), C->deep.f(), s, split);
+    // a zero column's frame values are zero too (ood_kernel), so deep_sz needs no list
+    launch_deep(C->lde.f(), C->clde.f(), roots, Ntab, dp, dD, C->xinv.f(), C->deep.f(), s, split, meta.deep,
+                meta.n_nonzero + (uint32_t)Cc);
   }
   check_launch("DEEP composition");
   T.mark(6);
@@ -1468,6 +1539,7 @@ int zkl_hip_device_alloc(zkl_ctx* c, size_t bytes, void** d) {
 int zkl_hip_device_free(zkl_ctx* c, void* d) {
   if (!c) return ZKL_E_INVALID;
   return run_guarded(c, [&] {
+    c->zero_stage.wrote(d, 0, sizeof(fe));  // a freed LDE buffer: its address may come back
     HIPCHECK(hipSetDevice(c->device));
     HIPCHECK(hipFree(d));
   });
@@ -1477,6 +1549,7 @@ int zkl_hip_memcpy(zkl_ctx* c, void* dst, const void* src, size_t bytes, int kin
   if (!c || kind < 1 || kind > 3) return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    if (kind != 2 && bytes) c->zero_stage.wrote(dst, bytes, sizeof(fe));
     HIPCHECK(hipSetDevice(c->device));
     hipMemcpyKind k = kind == 1 ? hipMemcpyHostToDevice : kind == 2 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     HIPCHECK(hipMemcpyAsync(dst, src, bytes, k, c->stream));
@@ -1502,6 +1575,7 @@ int zkl_hip_hash_rows(zkl_ctx* c, const void* d_m, uint32_t nc, uint32_t nr, uin
   if (!c || !d_m || !d_out || nc == 0 || np < 1 || np > 16 || rate < 1 || rate > 256) return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    c->zero_stage.forget();  // this call may write the caller's LDE buffers
     HIPCHECK(hipSetDevice(c->device));
     upload_hasher(c->stream);
     c->parts.ensure((size_t)std::max<uint32_t>(np, 1) * nr * sizeof(fe) + 16);
@@ -1557,6 +1631,7 @@ int zkl_hip_hash_rows_periodic(zkl_ctx* c, const void* d_m, uint32_t nc, uint32_
     return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    c->zero_stage.forget();  // this call may write the caller's LDE buffers
     HIPCHECK(hipSetDevice(c->device));
     upload_hasher(c->stream);
     c->parts.ensure((size_t)std::max<uint32_t>(np, 1) * nr * sizeof(fe) + 16);
@@ -1596,28 +1671,12 @@ int zkl_hip_lde_columns(zkl_ctx* c, const void* d_values, uint32_t nc, uint32_t 
         decode_column_scan(c->h_scan.at<uint32_t>(), nc, n, per.data());
       }
     }
-    const MontTab mi = mont_tab(c->miroots.p, c->tab_N), mr = mont_tab(c->mroots.p, c->tab_N);
-    int split = -1;
-    for (uint32_t c0 = 0; c0 < nc;) {
-      uint32_t c1 = c0;
-      const bool zero = per[c0] == 0;
-      while (c1 < nc && (per[c1] == 0) == zero) c1++;
-      fe* cf = (fe*)d_coeffs + (size_t)c0 * n;
-      fe* out = (fe*)d_lde + (size_t)c0 * N;
-      if (zero) {
-        HIPCHECK(hipMemsetAsync(cf, 0, (size_t)(c1 - c0) * n * sizeof(fe), s));
-        HIPCHECK(hipMemsetAsync(out, 0, (size_t)(c1 - c0) * N * sizeof(fe), s));
-      } else {
-        launch_intt_scaled((const fe*)d_values + (size_t)c0 * n, cf, c1 - c0, n, mi, c->tab_N, c->opow_n.f(), s);
-        const int sp = launch_lde_from_coeffs(cf, c1 - c0, n, N, mr, c->tab_N, out, s, want_split != 0);
-        if (split >= 0 && sp != split) throw std::runtime_error("internal: LDE column runs in different layouts");
-        split = sp;
-      }
-      c0 = c1;
-    }
+    const int split = trace_lde_columns(c, c->zero_stage, (const fe*)d_values, nc, n, N,
+                                        column_structure_enabled() ? per.data() : nullptr, (fe*)d_coeffs, (fe*)d_lde,
+                                        want_split != 0, nullptr, s);
     check_launch("stage entry point");
     HIPCHECK(hipStreamSynchronize(s));
-    if (split_out) *split_out = split < 0 ? 0 : split;
+    if (split_out) *split_out = split;
   });
 }
 
@@ -1653,6 +1712,7 @@ int zkl_hip_poseidon_permute(zkl_ctx* c, void* d_states, uint32_t n_states, int 
   if (!c || !d_states || engine < 0 || engine > 2) return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    c->zero_stage.forget();  // this call may write the caller's LDE buffers
     HIPCHECK(hipSetDevice(c->device));
     upload_hasher(c->stream);
     launch_permute((fe*)d_states, n_states, engine, c->stream);
@@ -1665,6 +1725,7 @@ int zkl_hip_merkle_tree(zkl_ctx* c, const void* d_leaves, uint32_t n, void* d_no
   if (!c || n < 2 || (n & (n - 1))) return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    c->zero_stage.forget();  // this call may write the caller's LDE buffers
     HIPCHECK(hipSetDevice(c->device));
     upload_hasher(c->stream);
     HIPCHECK(hipMemcpyAsync((fe*)d_nodes + n, d_leaves, (size_t)n * sizeof(fe), hipMemcpyDeviceToDevice, c->stream));
@@ -1679,6 +1740,7 @@ int zkl_hip_ntt(zkl_ctx* c, void* d_data, uint32_t nc, uint32_t n, int dif, int 
   if (!c || !d_data || n < 2 || (n & (n - 1))) return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    c->zero_stage.forget();  // this call may write the caller's LDE buffers
     HIPCHECK(hipSetDevice(c->device));
     ensure_tables(c, c->tab_n ? c->tab_n : n, std::max<size_t>(n, c->tab_N));
     const MontTab t = mont_tab(inverse ? c->miroots.p : c->mroots.p, c->tab_N);
@@ -1693,6 +1755,7 @@ int zkl_hip_lde(zkl_ctx* c, const void* d_values, uint32_t nc, uint32_t n, uint3
   if (!c || n < 2 || (n & (n - 1)) || blowup < 1 || (blowup & (blowup - 1))) return ZKL_E_INVALID;
   std::lock_guard<std::mutex> lk(c->mu);
   return run_guarded(c, [&] {
+    c->zero_stage.forget();  // this call may write the caller's LDE buffers
     HIPCHECK(hipSetDevice(c->device));
     size_t N = (size_t)n * blowup;
     ensure_tables(c, n, N);
