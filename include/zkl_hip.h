@@ -447,6 +447,20 @@ int zkl_build_segment_trace(const zkl_program* prog, uint32_t r_start, uint32_t 
                             uint8_t state_out[32]);
 void zkl_program_free(zkl_program* prog);
 
+/* n segment proofs verified as zkl_verify_segment verifies each (same checks, same verdict, same
+ * message), with the Poseidon hashing of the openings and the composition-coefficient draws on
+ * ctx's device.  ctx NULL: the same batch on host threads.  status_out[i] = ZKL_OK or
+ * ZKL_E_INVALID; errors_out (nullable) receives n NUL-terminated messages of
+ * ZKL_VERIFY_MSG_LEN bytes each ("" for a proof that verifies).  The call itself returns ZKL_OK
+ * when every proof got a verdict, a ZKL_E_* code when the batch could not be run.  opts[i] must
+ * equal the options recorded in proof i.  The replay is split into a host plan (parsing,
+ * transcript, every structural check) and flat hash jobs: only proofs that
+ * passed the structural checks contribute jobs, so corrupt bytes change values, never addresses. */
+#define ZKL_VERIFY_MSG_LEN 160
+int zkl_hip_verify_segments(zkl_ctx* ctx, const uint8_t* const* proofs, const size_t* lens,
+                            const zkl_air_public_inputs* pis, const zkl_proof_options* opts, uint32_t n,
+                            int32_t* status_out, char* errors_out);
+
 /* ---- zl1 step proof (host-side, no device work) ----------------------------------
  * StepProof::to_bytes (proof/step.rs:79-151) of the step proof prove_segment builds around
  * an inner proof from zkl_hip_prove_segment*: "ZKLSTP1" | lambda | suite | core pi |
@@ -504,10 +518,22 @@ typedef struct {
  * Each child's Fiat-Shamir transcript is replayed from its step proof alone (agg/fs.rs:38-245)
  * and every opening, DEEP value, FRI fold, remainder and PoW is checked; a child that fails
  * is rejected (ZKL_E_INVALID) rather than aggregated into an unsatisfiable trace.  The
- * artifact is freed with zkl_hip_free.  Host-only (no ctx, no device). */
+ * artifact is freed with zkl_hip_free.  Host-only (no ctx, no device); zkl_hip_agg_prove below
+ * hashes the child replays on a context's device. */
 int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                   const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                   uint8_t digest_out[32]);
+/* zkl_agg_prove with the child replay's hashing on ctx's device: same arguments, same artifact
+ * bytes, same digest, same rejections.  ctx NULL is zkl_agg_prove.  Rank 0 of a multi-GPU run
+ * holds a context after proving its own segments and can pass it here. */
+int zkl_hip_agg_prove(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
+                      const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
+                      uint8_t digest_out[32]);
+/* Wall times (ms) of the calling thread's last zkl_agg_prove / zkl_hip_agg_prove: [0] step decode +
+ * child replay on the host (parse, transcript, DEEP / FRI arithmetic, plan), [1] hashing of the
+ * replay (host executor or device incl. copies), [2] build_public + aggregation trace, [3] the
+ * ZlAggAir proof without grinding, [4] its grinding, [5] the whole call.  Returns number written. */
+int zkl_agg_last_times(double* out_ms, int max_n);
 /* RecursionArtifactCodec::decode (lib.rs:552-660) + RecursionBackend::verify (lib.rs:346-372)
  * -> verify_agg_proof (prove.rs:732-791): decodes a ZKLRC1 artifact and verifies the
  * aggregation proof under ZlAggAir and the artifact's public inputs, accepting proof options

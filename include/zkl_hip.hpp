@@ -310,6 +310,32 @@ inline void verify_proof(const Proof& proof, const AirPublicInputs& pi, const Pr
   detail::check(zkl_verify_segment(proof.bytes.data(), proof.bytes.size(), &pi, &opts.raw()));
 }
 
+// verify_proof over a batch (zkl_hip_verify_segments): one message per proof, empty when it
+// verifies, otherwise what verify_proof throws for that proof alone.  dev: the Poseidon hashing of
+// the openings and the composition-coefficient draws run on its GPU; nullptr: host threads.
+inline std::vector<std::string> verify_proofs(const std::vector<Proof>& proofs, const std::vector<AirPublicInputs>& pis,
+                                              const std::vector<ProofOptions>& opts, const Device* dev = nullptr) {
+  const size_t n = proofs.size();
+  if (pis.size() != n || opts.size() != n) throw Error(Error::Kind::Backend, ZKL_E_INVALID, "one statement per proof");
+  std::vector<const uint8_t*> ptrs(n);
+  std::vector<size_t> lens(n);
+  std::vector<zkl_air_public_inputs> pa(n);
+  std::vector<zkl_proof_options> oa(n);
+  for (size_t i = 0; i < n; i++) {
+    ptrs[i] = proofs[i].bytes.data();
+    lens[i] = proofs[i].bytes.size();
+    pa[i] = pis[i];
+    oa[i] = opts[i].raw();
+  }
+  std::vector<int32_t> st(n);
+  std::vector<char> msg(n * ZKL_VERIFY_MSG_LEN + 1);
+  detail::check(zkl_hip_verify_segments(dev ? dev->ctx() : nullptr, ptrs.data(), lens.data(), pa.data(), oa.data(),
+                                        (uint32_t)n, st.data(), msg.data()));
+  std::vector<std::string> out(n);
+  for (size_t i = 0; i < n; i++) out[i] = std::string(&msg[i * ZKL_VERIFY_MSG_LEN]);
+  return out;
+}
+
 // zl1 step metadata as prove_segment fills it (prove.rs:1103-1174): suite = program_id
 // (prove.rs:985), the boundary bytes fe_to_bytes_fold of the AIR public inputs' pc_init, RAM
 // grand products and ROM lanes (SegmentBoundaryBytes, prove.rs:1112), the segment position and
@@ -381,8 +407,10 @@ struct WinterfellBackend {
     std::vector<uint8_t> bytes;  // ZKLRC1 (proof.bin)
     Digest recursion_digest;
   };
+  // dev (optional): the child replays' Poseidon hashing runs on its GPU (zkl_hip_agg_prove) -- same
+  // artifact, digest and rejections; the aggregating rank has one after proving its own segments
   static Artifact prove(const std::vector<StepProof>& steps, const ProverOptions& opts,
-                        uint32_t trace_mode = ZKL_AGG_TRACE_VALID) {
+                        uint32_t trace_mode = ZKL_AGG_TRACE_VALID, const Device* dev = nullptr) {
     std::vector<const uint8_t*> ptrs;
     std::vector<size_t> lens;
     for (const auto& s : steps) {
@@ -393,11 +421,18 @@ struct WinterfellBackend {
     uint8_t* out = nullptr;
     size_t len = 0;
     Artifact a{};
-    const int rc = zkl_agg_prove(ptrs.data(), lens.data(), (uint32_t)steps.size(), &o, &out, &len,
-                                 a.recursion_digest.data());
+    const int rc = zkl_hip_agg_prove(dev ? dev->ctx() : nullptr, ptrs.data(), lens.data(), (uint32_t)steps.size(), &o,
+                                     &out, &len, a.recursion_digest.data());
     detail::check(rc, nullptr, rc == ZKL_E_INVALID ? Error::Kind::RecursionInvalid : Error::Kind::Backend);
     a.bytes = detail::take(out, len);
     return a;
+  }
+  // wall times (ms) of this thread's last prove(): replay on the host, its hashing, aggregation
+  // trace, ZlAggAir proof without grinding, grinding, whole call (zkl_agg_last_times)
+  static std::array<double, 6> last_times() {
+    std::array<double, 6> t{};
+    zkl_agg_last_times(t.data(), 6);
+    return t;
   }
   static void verify(const std::vector<uint8_t>& artifact, uint32_t min_security_bits) {
     const int rc = zkl_agg_verify(artifact.data(), artifact.size(), min_security_bits);

@@ -12,9 +12,11 @@
 //   artifact / digest      ZKLRC1 (lib.rs:486-551), recursion_digest_from_agg_pi (prove.rs:585-616)
 //
 // Where it runs: the aggregation trace has one row per child (>= 8 rows, 64 for BASELINE
-// configs[3]), so the whole proof is ~10^4 Poseidon permutations plus 2^16 grinding tries.
-// A GPU launch costs more than the work, so it stays on the host (the grinding search runs on
-// host threads); the segment proofs it consumes are the GPU's output.
+// configs[3]), so the ZlAggAir proof is ~10^4 Poseidon permutations plus 2^16 grinding tries and
+// stays on the host (the grinding search runs on host threads).  The child replays before it are
+// ~10^4 permutations per child: their hashing goes through the hash plan of proof_view.h, on
+// host threads (zkl_agg_prove) or on a context's device (zkl_hip_agg_prove); DESIGN.md §10 has
+// the measured split.
 //
 // Quadratic extension (winter-math 0.13.1, f128 `ExtensibleField<2>` [WF-recall]): elements
 // a + b*phi with phi^2 = phi - 1, mul = [a0 b0 - a1 b1, (a0 + a1)(b0 + b1) - a0 b0], Frobenius
@@ -25,6 +27,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -43,6 +46,12 @@ void children_root(const uint8_t suite[32], const uint8_t* digests, const uint8_
 namespace {
 
 struct AggError : std::invalid_argument { using std::invalid_argument::invalid_argument; };
+
+// wall times of the calling thread's last aggregation proof (zkl_agg_last_times)
+thread_local double g_agg_ms[6] = {0, 0, 0, 0, 0, 0};
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // ------------------------------------------------------------------ quadratic extension
 struct fe2 {
@@ -351,16 +360,6 @@ zkl_air_public_inputs replay_pi(const StepDecoded& s) {
   pi.vm_usage_mask = s.vm_usage_mask;
   pi.ram_delta_clk_bits = s.ram_delta_clk_bits;
   return pi;
-}
-
-Child load_child(const uint8_t* p, size_t n) {
-  Child c;
-  c.step = decode_step(p, n);
-  const zkl_air_public_inputs pi = replay_pi(c.step);
-  const std::string e = verify_segment_ex(c.step.inner, c.step.inner_len, pi, nullptr, &c.v, false);
-  if (!e.empty()) throw AggError("child step proof does not replay: " + e);
-  if (c.v.fri_roots.size() < 2) throw AggError("AggTrace requires at least two FRI layers per child");
-  return c;
 }
 
 // ------------------------------------------------------------------ aggregation trace
@@ -911,6 +910,7 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   // 7. grinding: smallest nonce >= 1 (host threads; winterfell without `concurrent` searches
   // sequentially, so the minimum is what it finds)
   uint64_t nonce = 1;
+  const auto t_grind = std::chrono::steady_clock::now();
   if (ao.grind > 0) {
     const fe sd = coin.seed;
     const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
@@ -936,6 +936,7 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
     for (auto& t : th) t.join();
     nonce = best.load();
   }
+  g_agg_ms[4] = ms_since(t_grind);
   // 8. query positions: draw_integers(q, N, nonce), sort, dedup
   coin.seed = H.merge_with_int(coin.seed, nonce);
   coin.counter = 0;
@@ -1327,27 +1328,43 @@ std::string verify_artifact(const uint8_t* art, size_t len, uint32_t min_bits) {
 using namespace zkl;
 
 namespace {
-std::vector<Child> load_children(const uint8_t* const* steps, const size_t* lens, uint32_t n) {
+// exec runs the hash plans of the child replays (host threads or a context's device); ms
+// (nullable) accumulates [0] decode + host replay, [1] hashing
+std::vector<Child> load_children(const uint8_t* const* steps, const size_t* lens, uint32_t n, const PlanExec& exec,
+                                 size_t cap, double* ms) {
   if (!steps || !lens || n == 0) throw AggError("RecursionBackend::recursion_prove requires at least one step proof");
   for (uint32_t i = 0; i < n; i++)
     if (!steps[i]) throw AggError("null step proof");
-  // children replay independently (~10^4 host permutations each at 2^16 rows): host threads
+  // children replay independently (~10^4 permutations each at 2^16 rows): decoded and planned on
+  // host threads, hashed by exec, each replay being verify_segment_ex without the out-of-domain
+  // identity (agg/fs.rs:38-245)
   std::vector<Child> ch(n);
   std::vector<std::string> err(n);
-  std::atomic<uint32_t> next{0};
-  const unsigned nt = std::max(1u, std::min<unsigned>(std::min(16u, std::thread::hardware_concurrency()), n));
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; t++)
-    th.emplace_back([&] {
-      for (uint32_t i; (i = next.fetch_add(1)) < n;) {
-        try {
-          ch[i] = load_child(steps[i], lens[i]);
-        } catch (const std::exception& e) {
-          err[i] = e.what();
-        }
-      }
-    });
-  for (auto& x : th) x.join();
+  std::vector<zkl_air_public_inputs> pis(n);
+  const auto t0 = std::chrono::steady_clock::now();
+  parallel_for(n, [&](size_t i) {
+    try {
+      ch[i].step = decode_step(steps[i], lens[i]);
+      pis[i] = replay_pi(ch[i].step);
+    } catch (const std::exception& e) {
+      err[i] = e.what();
+    }
+  });
+  if (ms) ms[0] += ms_since(t0);
+  std::vector<BatchItem> items;
+  std::vector<uint32_t> who;
+  for (uint32_t i = 0; i < n; i++)
+    if (err[i].empty()) {
+      items.push_back({ch[i].step.inner, ch[i].step.inner_len, &pis[i], nullptr, &ch[i].v});
+      who.push_back(i);
+    }
+  std::vector<std::string> verr(items.size());
+  verify_segments_batch(items.data(), items.size(), false, exec, cap, verr.data(), ms);
+  for (size_t k = 0; k < who.size(); k++) {
+    const uint32_t i = who[k];
+    if (!verr[k].empty()) err[i] = "child step proof does not replay: " + verr[k];
+    else if (ch[i].v.fri_roots.size() < 2) err[i] = "AggTrace requires at least two FRI layers per child";
+  }
   for (uint32_t i = 0; i < n; i++)
     if (!err[i].empty()) throw AggError("child " + std::to_string(i) + ": " + err[i]);
   for (const Child& c : ch)
@@ -1364,14 +1381,19 @@ AggPi public_of(const std::vector<Child>& ch) {
 
 extern "C" {
 
-int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps, const zkl_agg_options* opts,
-                  uint8_t** artifact_out, size_t* artifact_len, uint8_t digest_out[32]) {
+static int agg_prove_with(const PlanExec& exec, size_t cap, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
+                          const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
+                          uint8_t digest_out[32]) {
   if (!opts || !artifact_out || !artifact_len) return ZKL_E_INVALID;
   std::vector<uint8_t> art;
+  const auto t_call = std::chrono::steady_clock::now();
+  for (double& x : g_agg_ms) x = 0;
   const int rc = guarded_call([&] {
-    const std::vector<Child> ch = load_children(steps, step_lens, n_steps);
+    const std::vector<Child> ch = load_children(steps, step_lens, n_steps, exec, cap, g_agg_ms);
+    auto t0 = std::chrono::steady_clock::now();
     const AggPi pi = public_of(ch);  // build_public; prove() re-derives suite / count / ms identically
     const auto T = build_agg_trace(pi, ch, opts->trace_mode);
+    g_agg_ms[2] = ms_since(t0);
     AggOpts ao{std::max<uint32_t>(opts->queries, 16), opts->blowup, opts->grind,
                opts->min_security_bits >= 128 ? 2u : 1u};
     if (ao.queries > 255) throw AggError("queries must be at most 255");
@@ -1385,17 +1407,39 @@ int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t
     }
     const std::vector<fe> el = agg_pi_elements(pi);
     ao.check_air = opts->trace_mode == ZKL_AGG_TRACE_VALID;
+    t0 = std::chrono::steady_clock::now();
     const std::vector<uint8_t> proof =
         ao.field_ext == 2 ? prove_air<fe2>(T, el, pi, ao) : prove_air<fe>(T, el, pi, ao);
+    g_agg_ms[3] = ms_since(t0) - g_agg_ms[4];
     art = encode_artifact(pi, proof);
     if (digest_out) recursion_digest(pi, digest_out);
   });
+  g_agg_ms[5] = ms_since(t_call);
   if (rc) return rc;
   *artifact_out = (uint8_t*)malloc(art.size());
   if (!*artifact_out) return ZKL_E_OOM;
   memcpy(*artifact_out, art.data(), art.size());
   *artifact_len = art.size();
   return ZKL_OK;
+}
+
+int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps, const zkl_agg_options* opts,
+                  uint8_t** artifact_out, size_t* artifact_len, uint8_t digest_out[32]) {
+  return agg_prove_with(host_plan_exec(), 0, steps, step_lens, n_steps, opts, artifact_out, artifact_len, digest_out);
+}
+
+int zkl_hip_agg_prove(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
+                      const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
+                      uint8_t digest_out[32]) {
+  return agg_prove_with(ctx ? device_plan_exec(ctx) : host_plan_exec(), ctx ? PLAN_DEVICE_CAP : 0, steps, step_lens, n_steps, opts, artifact_out,
+                        artifact_len, digest_out);
+}
+
+int zkl_agg_last_times(double* out_ms, int max_n) {
+  if (!out_ms || max_n <= 0) return 0;
+  const int k = std::min(max_n, 6);
+  for (int i = 0; i < k; i++) out_ms[i] = g_agg_ms[i];
+  return k;
 }
 
 int zkl_agg_verify(const uint8_t* artifact, size_t len, uint32_t min_security_bits) {
@@ -1415,7 +1459,7 @@ int zkl_agg_trace_mode(const uint8_t* const* steps, const size_t* step_lens, uin
                        zkl_f128* out, uint32_t max_rows, uint32_t* rows_out) {
   if (!rows_out || trace_mode > ZKL_AGG_TRACE_REFERENCE) return ZKL_E_INVALID;
   return guarded_call([&] {
-    const std::vector<Child> ch = load_children(steps, step_lens, n_steps);
+    const std::vector<Child> ch = load_children(steps, step_lens, n_steps, host_plan_exec(), 0, nullptr);
     const auto T = build_agg_trace(public_of(ch), ch, trace_mode);
     const uint32_t rows = (uint32_t)T[0].size();
     *rows_out = rows;

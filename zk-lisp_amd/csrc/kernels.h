@@ -137,6 +137,16 @@ size_t row_prefix_table_bytes(const RowPrefixPlan& plan);
 bool launch_hash_rows_prefix(const fe* d_mat, uint32_t n_cols, size_t n_rows, uint32_t num_partitions,
                              uint32_t hash_rate, const RowPrefixPlan& plan, uint32_t* d_table, fe* d_tmp, fe* d_out,
                              hipStream_t s, int split = 0);
+// Batch verification: jobs over one device buffer of field elements.
+// launch_open_rows: buf[dst] = row digest of the contiguous row buf[src .. src + ncols) (chunks of
+// psize columns, merge_many when `merge`), one launch per row shape; launch_merge_jobs:
+// buf[dst] = merge(buf[left], buf[right]), one launch per tree height.  The caller bounds every
+// index against the buffer before upload.
+struct OpenRowJob { uint32_t src, dst; };
+struct MergeNodeJob { uint32_t left, right, dst; };
+void launch_open_rows(fe* d_buf, const OpenRowJob* d_jobs, size_t njobs, uint32_t ncols, uint32_t psize, uint32_t merge,
+                      hipStream_t s);
+void launch_merge_jobs(fe* d_buf, const MergeNodeJob* d_jobs, size_t njobs, hipStream_t s);
 // Merkle tree: d_nodes[n..2n) must hold the leaves; fills d_nodes[1..n).
 // coin_mode (d_coin, d_root_out): the transcript step after the tree runs in the launch that
 // reaches the root -- 1: coin[0] = merge(coin[0], root) (the trace / constraint root reseed), 2:

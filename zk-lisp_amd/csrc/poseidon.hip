@@ -500,6 +500,58 @@ __global__ PG_KERNEL void grind_kernel(fe seed, const fe* seed_p, uint64_t base,
   }
 }
 
+// ---- batch verification: the jobs of a hash plan over one buffer of field
+// elements, inputs first, computed digests after.  The host builds the jobs only from proofs
+// that passed every structural check and bounds every index before upload (prover.cpp).
+// One group per row job: hash_rows_kernel's work on a contiguous (row-major) row buf[src ..).
+// A launch carries one row shape, so every group of a wave runs the same number of permutations.
+__global__ PG_KERNEL void open_rows_kernel(fe* buf, const OpenRowJob* __restrict__ jobs, size_t njobs, uint32_t ncols,
+                                           uint32_t psize, uint32_t merge) {
+  PG_SETUP();
+  const bool live = P.g < PG_PER_WAVE && item < njobs;
+  const OpenRowJob job = live ? jobs[item] : OpenRowJob{0, 0};
+  const uint32_t np = (ncols + psize - 1) / psize;
+  fe keep0 = fe_zero(), keep1 = fe_zero(), d = fe_zero();
+  for (uint32_t p = 0; p < np; p++) {
+    const uint32_t c0 = p * psize;
+    const uint32_t len = min(psize, ncols - c0);
+    const fe* base = buf + job.src + c0;
+    d = pg_sponge<DOM_ELEMS>(P, live, (int)((len + 1) / 2), [&](int j) {
+      fe a = base[2 * j];
+      fe b = (2u * j + 1 < len) ? base[2 * j + 1] : fe_zero();
+      return fold_pair(a, b);
+    });
+    if (merge) {  // message p of merge_many is absorbed by lane (p+1) % 10 of block (p+1) / 10
+      fe v = pg_bcast(P, d, 0);
+      if ((int)((p + 1) % 10) == P.j) {
+        if (p + 1 < 10) keep0 = v; else keep1 = v;
+      }
+    }
+  }
+  if (merge) d = pg_sponge<DOM_MANY>(P, live, (int)np, [&](int i) { return i + 1 < 10 ? keep0 : keep1; });
+  if (live && P.j == 0) buf[job.dst] = d;
+}
+
+// one group per merge job: buf[dst] = merge(buf[left], buf[right]); a launch carries one height
+__global__ PG_KERNEL void merge_jobs_kernel(fe* buf, const MergeNodeJob* __restrict__ jobs, size_t njobs) {
+  PG_SETUP();
+  const bool live = P.g < PG_PER_WAVE && item < njobs;
+  const MergeNodeJob job = live ? jobs[item] : MergeNodeJob{0, 0, 0};
+  fe d = pg_sponge<DOM_MERGE>(P, live, 2, [&](int j) { return buf[j == 0 ? job.left : job.right]; });
+  if (live && P.j == 0) buf[job.dst] = d;
+}
+
+void launch_open_rows(fe* d_buf, const OpenRowJob* d_jobs, size_t njobs, uint32_t ncols, uint32_t psize, uint32_t merge,
+                      hipStream_t s) {
+  if (!njobs) return;
+  if (!ncols || !psize || (ncols + psize - 1) / psize > 16) throw std::logic_error("launch_open_rows: row shape out of range");
+  open_rows_kernel<<<pg_blocks(njobs), 256, 0, s>>>(d_buf, d_jobs, njobs, ncols, psize, merge);
+}
+void launch_merge_jobs(fe* d_buf, const MergeNodeJob* d_jobs, size_t njobs, hipStream_t s) {
+  if (!njobs) return;
+  merge_jobs_kernel<<<pg_blocks(njobs), 256, 0, s>>>(d_buf, d_jobs, njobs);
+}
+
 // Row-digest rule for one-chunk partitioned rows (partition size > width): 0 = winterfell
 // commit_to_rows (merge_many of the single chunk digest), 1 = agg/child.rs:1025-1045
 // (the chunk digest itself).  DESIGN.md §3.1; the oracle has the same switch.

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/zkl_hip.h"
+#include "air_host.h"
 #include "field.h"
 
 namespace zkl {
@@ -34,6 +35,63 @@ struct Rd {
 // digests; consumes the proof bytes from r.  Returns false if the proof is malformed.
 bool batch_merkle_root(Rd& r, size_t n_leaves, const std::vector<size_t>& idx, const std::vector<fe>& leaves,
                        fe* root);
+
+// ---- hash plan: the Poseidon work of a replay as flat jobs over one index
+// space of field elements.  An index below PLAN_OUT addresses `in` (values parsed from the
+// proof), PLAN_OUT | k the k-th computed digest.  Built only from proofs that passed every
+// structural check, so a corrupted proof changes the values in `in`, never an index.
+constexpr uint32_t PLAN_OUT = 0x80000000u;
+struct HashPlan {
+  // row digest of in[src .. src + ncols): chunks of psize columns through hash_elements, then
+  // merge_many of the chunk digests when `merge`, else the single chunk's digest (the one-chunk
+  // rule is resolved by whoever appends the job).  A FRI leaf is ncols = psize = 2, no merge.
+  struct RowJob { uint32_t src, ncols, psize, merge, dst; };
+  struct MergeJob { uint32_t left, right, dst; };   // dst = merge(left, right)
+  struct DrawJob { fe seed; uint32_t count, dst; };  // dst + k = merge_with_int(seed, k + 1)
+  std::vector<fe> in;
+  uint32_t n_out = 0;
+  std::vector<RowJob> rows;
+  std::vector<std::vector<MergeJob>> merges;  // merges[h - 1]: height h above the leaves; reads
+                                              // only inputs, row digests and lower heights
+  std::vector<DrawJob> draws;
+  uint32_t add_in(const fe* v, size_t n) {
+    const uint32_t at = (uint32_t)in.size();
+    in.insert(in.end(), v, v + n);
+    return at;
+  }
+  uint32_t new_out(uint32_t n = 1) {
+    const uint32_t at = PLAN_OUT | n_out;
+    n_out += n;
+    return at;
+  }
+  // snapshot / rollback: an opening rejected after some of its jobs were appended leaves none
+  struct Mark { size_t in, rows, draws; uint32_t n_out; std::vector<size_t> merges; };
+  Mark mark() const {
+    Mark m{in.size(), rows.size(), draws.size(), n_out, {}};
+    for (const auto& l : merges) m.merges.push_back(l.size());
+    return m;
+  }
+  void rewind(const Mark& m) {
+    in.resize(m.in);
+    rows.resize(m.rows);
+    draws.resize(m.draws);
+    n_out = m.n_out;
+    for (size_t h = 0; h < merges.size(); h++) merges[h].resize(h < m.merges.size() ? m.merges[h] : 0);
+  }
+  void add_merge(size_t height, uint32_t l, uint32_t r, uint32_t dst) {
+    if (merges.size() < height) merges.resize(height);
+    merges[height - 1].push_back({l, r, dst});
+  }
+};
+// The plan of BatchMerkleProof::get_root (winter-crypto 0.13) for sorted unique leaf indices
+// whose digests are the plan nodes `leaves`: parses the proof bytes from r, makes every
+// structural rejection (depth byte, list shape, sharing, every proof node consumed, final
+// index 1) and appends the merges; *root receives the root's node.  Nothing is hashed.
+bool plan_batch_merkle(Rd& r, size_t n_leaves, const std::vector<size_t>& idx, const std::vector<uint32_t>& leaves,
+                       HashPlan& plan, uint32_t* root);
+// Host execution with hasher(): out[k] = value of node PLAN_OUT | k.  par_draws: large draw
+// ranges are split over host threads (a single proof; a batch already has a thread per proof).
+void run_plan_host(const HashPlan& plan, std::vector<fe>& out, bool par_draws);
 
 struct SegmentView {
   // context
@@ -83,6 +141,57 @@ std::string verify_segment(const uint8_t* proof, size_t len, const zkl_air_publi
 // VM output, so the identity is not available there either).
 std::string verify_segment_ex(const uint8_t* proof, size_t len, const zkl_air_public_inputs& pi,
                               const zkl_proof_options* opts, SegmentView* view, bool check_ood);
+
+// ---- deferred replay: verify_segment_ex split into "plan" and "hash" ---------
+// replay_segment does everything verify_segment_ex does that needs no opening digest (parsing,
+// transcript, positions, DEEP values, FRI folds, remainder) and appends the rest to R.plan,
+// recording each deferred check at its place in the check sequence.  A host-side failure ends
+// the replay where verify_segment_ex ends (R.host_err; every recorded check precedes it).
+// finish_replay, given the plan's results, returns the verdict: the message of the failing
+// check with the lowest sequence position -- what verify_segment_ex returns for the same bytes.
+struct SegmentReplay {
+  HashPlan plan;
+  struct Check {
+    uint32_t node;    // computed root; PLAN_OUT - 1: the out-of-domain identity over the drawn coefficients
+    fe want;          // committed root
+    const char* msg;
+  };
+  std::vector<Check> checks;
+  struct Fix { uint32_t node; fe* dst; };  // *dst = node once the proof verifies (SegmentView::*_root_ref)
+  std::vector<Fix> fixes;
+  std::string host_err;
+  AirInstance air;          // kept for the out-of-domain identity
+  uint32_t ood_draws = 0;   // node of the first drawn coefficient (alphas, then betas)
+  SegmentView local;
+  SegmentView* view = nullptr;
+};
+void replay_segment(const uint8_t* proof, size_t len, const zkl_air_public_inputs& pi, const zkl_proof_options* opts,
+                    SegmentView* view, bool check_ood, SegmentReplay& R);
+std::string finish_replay(SegmentReplay& R, const fe* out);
+
+// Executes plans[0..n): outs[i] receives a pointer to plan i's n_out results, valid until the
+// executor's next call.  host_plan_exec runs them on host threads; device_plan_exec
+// (prover.cpp) on a context's device under its lock.
+using PlanExec = std::function<void(const HashPlan* const* plans, size_t n, const fe** outs)>;
+PlanExec host_plan_exec();
+PlanExec device_plan_exec(zkl_ctx* ctx);
+// f(i) for i < n on at most 16 host threads; the first exception is rethrown after the join
+void parallel_for(size_t n, const std::function<void(size_t)>& f);
+
+// A batch of proofs through replay_segment / exec / finish_replay, in waves of proofs planned
+// on host threads and submissions of at most `cap` field elements of input + output (0: a whole
+// wave at once, for the host executor, which stages nothing; PLAN_DEVICE_CAP for a device).  errs[i] = verify_segment_ex's message for
+// item i.  ms (nullable) accumulates wall time: [0] host replay and verdicts, [1] exec.
+struct BatchItem {
+  const uint8_t* proof;
+  size_t len;
+  const zkl_air_public_inputs* pi;
+  const zkl_proof_options* opts;  // nullable: taken from the proof
+  SegmentView* view;              // nullable
+};
+constexpr size_t PLAN_DEVICE_CAP = (size_t)1 << 22;  // 64 MiB of device buffer, as much pinned staging
+void verify_segments_batch(const BatchItem* items, size_t n, bool check_ood, const PlanExec& exec, size_t cap,
+                           std::string* errs, double* ms);
 
 // A decoded ZKLSTP1 step proof (StepProof::from_bytes, proof/step.rs:153-493) with the
 // derived StepMeta (step.rs:516-533), zl1 root_trace (format.rs:214-238) and step digest

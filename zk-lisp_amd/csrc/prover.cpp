@@ -17,6 +17,7 @@
 #include <mutex>
 #include <set>
 #include <thread>
+#include <tuple>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -173,6 +174,10 @@ struct zkl_ctx {
   // zkl_hip_trace_buffer: pinned host traces the caller fills in place (two slots: one filled
   // while the other's proof runs); zkl_hip_prove_segment DMAs columns straight from them
   HBuf tbuf[ZKL_TRACE_BUFFERS];
+  // batch verification (zkl_hip_verify_segments, zkl_hip_agg_prove): one buffer of field elements
+  // (inputs, then computed digests), the job lists, and their pinned staging
+  DBuf vbuf, vjobs;
+  HBuf h_vin, h_vout;
 };
 
 static const char* kFamilyNames =
@@ -1267,6 +1272,130 @@ int run_guarded(zkl_ctx* ctx, const std::function<void()>& f) {
 // thread-local last-error string
 int zkl::guarded_call(const std::function<void()>& f) { return run_guarded(nullptr, f); }
 
+// ====================================================================== batch verification
+// Device execution of hash plans (proof_view.h).  The plans of one submission
+// are laid out in one index space -- every plan's inputs, then every plan's results -- and run
+// as one launch per row shape, one per tree height and one per draw range.  Every index is
+// bounded here, against the sizes of its own plan, before anything is uploaded: a mismatch is
+// a defect of the plan builder (std::logic_error, ZKL_E_INTERNAL), never a verdict.
+namespace {
+void run_plans_device(zkl_ctx* C, const HashPlan* const* plans, size_t n, const fe** outs) {
+  auto bad = [](const char* what) { throw std::logic_error(std::string("hash plan: ") + what); };
+  std::vector<size_t> in_base(n), out_base(n);
+  size_t tin = 0, tout = 0;
+  for (size_t i = 0; i < n; i++) {
+    in_base[i] = tin;
+    out_base[i] = tout;
+    tin += plans[i]->in.size();
+    tout += plans[i]->n_out;
+  }
+  if (tin + tout >= (size_t)PLAN_OUT) bad("submission exceeds the index space");
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<OpenRowJob>> rows;  // by (ncols, psize, merge)
+  std::vector<std::vector<MergeNodeJob>> merges;
+  struct Draw { fe seed; size_t count, dst; };
+  std::vector<Draw> draws;
+  std::vector<uint8_t> lvl;  // per result of a plan: the height that computes it (0 = row digest, 255 = none yet)
+  for (size_t i = 0; i < n; i++) {
+    const HashPlan& p = *plans[i];
+    const size_t nin = p.in.size(), nout = p.n_out;
+    lvl.assign(nout, 255);
+    auto out_ix = [&](uint32_t x) -> size_t {
+      if (!(x & PLAN_OUT) || (x & ~PLAN_OUT) >= nout) bad("result index out of range");
+      return x & ~PLAN_OUT;
+    };
+    for (const HashPlan::RowJob& j : p.rows) {
+      if ((j.src & PLAN_OUT) || !j.ncols || !j.psize || j.psize > j.ncols || (size_t)j.src + j.ncols > nin ||
+          (j.ncols + j.psize - 1) / j.psize > 16 || (!j.merge && j.psize != j.ncols))
+        bad("row job out of range");
+      const size_t d = out_ix(j.dst);
+      if (lvl[d] != 255) bad("result written twice");
+      lvl[d] = 0;
+      rows[std::make_tuple(j.ncols, j.psize, j.merge ? 1u : 0u)].push_back(
+          {(uint32_t)(in_base[i] + j.src), (uint32_t)(tin + out_base[i] + d)});
+    }
+    if (p.merges.size() > 200) bad("tree too deep");
+    if (merges.size() < p.merges.size()) merges.resize(p.merges.size());
+    for (size_t h = 0; h < p.merges.size(); h++)
+      for (const HashPlan::MergeJob& j : p.merges[h]) {
+        uint32_t a[2];
+        for (int t = 0; t < 2; t++) {
+          const uint32_t x = t ? j.right : j.left;
+          if (x & PLAN_OUT) {
+            const size_t o = out_ix(x);
+            if (lvl[o] > h) bad("merge reads a result of its own or a later height");
+            a[t] = (uint32_t)(tin + out_base[i] + o);
+          } else {
+            if (x >= nin) bad("merge input out of range");
+            a[t] = (uint32_t)(in_base[i] + x);
+          }
+        }
+        const size_t d = out_ix(j.dst);
+        if (lvl[d] != 255) bad("result written twice");
+        lvl[d] = (uint8_t)(h + 1);
+        merges[h].push_back({a[0], a[1], (uint32_t)(tin + out_base[i] + d)});
+      }
+    for (const HashPlan::DrawJob& j : p.draws) {
+      const size_t d = out_ix(j.dst);
+      if (d + j.count > nout) bad("draw range out of range");
+      for (size_t k = 0; k < j.count; k++) {
+        if (lvl[d + k] != 255) bad("result written twice");
+        lvl[d + k] = 0;
+      }
+      draws.push_back({j.seed, j.count, tin + out_base[i] + d});
+    }
+  }
+  size_t job_bytes = 0;
+  for (const auto& kv : rows) job_bytes += kv.second.size() * sizeof(OpenRowJob);
+  for (const auto& m : merges) job_bytes += m.size() * sizeof(MergeNodeJob);
+
+  HIPCHECK(hipSetDevice(C->device));
+  hipStream_t s = C->stream;
+  upload_hasher(s);
+  const size_t in_bytes = tin * sizeof(fe), out_bytes = tout * sizeof(fe);
+  C->h_vin.ensure(std::max<size_t>(in_bytes + job_bytes, 16));
+  C->h_vout.ensure(std::max<size_t>(out_bytes, 16));
+  C->vbuf.ensure(std::max<size_t>(in_bytes + out_bytes, 16));
+  C->vjobs.ensure(std::max<size_t>(job_bytes, 16));
+  for (size_t i = 0; i < n; i++)
+    if (!plans[i]->in.empty()) memcpy(C->h_vin.at<fe>() + in_base[i], plans[i]->in.data(), plans[i]->in.size() * sizeof(fe));
+  char* hj = C->h_vin.at<char>(in_bytes);
+  size_t off = 0;
+  for (const auto& kv : rows) {
+    memcpy(hj + off, kv.second.data(), kv.second.size() * sizeof(OpenRowJob));
+    off += kv.second.size() * sizeof(OpenRowJob);
+  }
+  for (const auto& m : merges) {
+    if (!m.empty()) memcpy(hj + off, m.data(), m.size() * sizeof(MergeNodeJob));
+    off += m.size() * sizeof(MergeNodeJob);
+  }
+  if (in_bytes) HIPCHECK(hipMemcpyAsync(C->vbuf.p, C->h_vin.p, in_bytes, hipMemcpyHostToDevice, s));
+  if (job_bytes) HIPCHECK(hipMemcpyAsync(C->vjobs.p, hj, job_bytes, hipMemcpyHostToDevice, s));
+  fe* buf = C->vbuf.f();
+  off = 0;
+  for (const auto& kv : rows) {
+    launch_open_rows(buf, (const OpenRowJob*)((const char*)C->vjobs.p + off), kv.second.size(), std::get<0>(kv.first),
+                     std::get<1>(kv.first), std::get<2>(kv.first), s);
+    off += kv.second.size() * sizeof(OpenRowJob);
+  }
+  for (const auto& m : merges) {
+    launch_merge_jobs(buf, (const MergeNodeJob*)((const char*)C->vjobs.p + off), m.size(), s);
+    off += m.size() * sizeof(MergeNodeJob);
+  }
+  for (const Draw& d : draws) launch_draws(d.seed, 0, d.count, buf + d.dst, s);
+  check_launch("batch verification");
+  if (out_bytes) HIPCHECK(hipMemcpyAsync(C->h_vout.p, buf + tin, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n; i++) outs[i] = C->h_vout.at<fe>() + out_base[i];
+}
+}  // namespace
+
+PlanExec zkl::device_plan_exec(zkl_ctx* ctx) {
+  return [ctx](const HashPlan* const* plans, size_t n, const fe** outs) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    run_plans_device(ctx, plans, n, outs);
+  };
+}
+
 // ====================================================================== C ABI
 extern "C" {
 
@@ -1465,6 +1594,30 @@ int zkl_verify_segment(const uint8_t* proof, size_t len, const zkl_air_public_in
   return run_guarded(nullptr, [&] {
     const std::string e = verify_segment(proof, len, *pi, *opts, nullptr);
     if (!e.empty()) throw InvalidArg(e);
+  });
+}
+
+int zkl_hip_verify_segments(zkl_ctx* ctx, const uint8_t* const* proofs, const size_t* lens,
+                            const zkl_air_public_inputs* pis, const zkl_proof_options* opts, uint32_t n,
+                            int32_t* status_out, char* errors_out) {
+  if (n == 0) return ZKL_OK;
+  if (!status_out || !proofs || !lens || !pis || !opts) return ZKL_E_INVALID;
+  for (uint32_t i = 0; i < n; i++)
+    if (!proofs[i]) return ZKL_E_INVALID;
+  return run_guarded(nullptr, [&] {
+    std::vector<BatchItem> items(n);
+    for (uint32_t i = 0; i < n; i++) items[i] = {proofs[i], lens[i], &pis[i], &opts[i], nullptr};
+    std::vector<std::string> errs(n);
+    verify_segments_batch(items.data(), n, true, ctx ? device_plan_exec(ctx) : host_plan_exec(),
+                          ctx ? PLAN_DEVICE_CAP : 0, errs.data(), nullptr);
+    for (uint32_t i = 0; i < n; i++) {
+      status_out[i] = errs[i].empty() ? ZKL_OK : ZKL_E_INVALID;
+      if (errors_out) {
+        char* e = errors_out + (size_t)i * ZKL_VERIFY_MSG_LEN;
+        memset(e, 0, ZKL_VERIFY_MSG_LEN);
+        memcpy(e, errs[i].data(), std::min<size_t>(errs[i].size(), ZKL_VERIFY_MSG_LEN - 1));
+      }
+    }
   });
 }
 

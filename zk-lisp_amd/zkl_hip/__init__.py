@@ -187,6 +187,11 @@ def load_library():
     lib.zkl_program_free.argtypes = [C.c_void_p]
     lib.zkl_agg_prove.argtypes = [P(C.c_char_p), P(C.c_size_t), C.c_uint32, P(AggOptions), P(P(C.c_uint8)),
                                   P(C.c_size_t), C.c_void_p]
+    lib.zkl_hip_agg_prove.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_uint32, P(AggOptions),
+                                      P(P(C.c_uint8)), P(C.c_size_t), C.c_void_p]
+    lib.zkl_agg_last_times.argtypes = [P(C.c_double), C.c_int]
+    lib.zkl_hip_verify_segments.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), P(AirPublicInputs),
+                                            P(ProofOptions), C.c_uint32, P(C.c_int32), C.c_char_p]
     lib.zkl_agg_verify.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
     lib.zkl_agg_trace.argtypes = [P(C.c_char_p), P(C.c_size_t), C.c_uint32, C.c_void_p, C.c_uint32, P(C.c_uint32)]
     lib.zkl_agg_trace_mode.argtypes = [P(C.c_char_p), P(C.c_size_t), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
@@ -219,19 +224,39 @@ def _steps_args(steps):
     return arr, lens
 
 
-def agg_prove(steps, queries=64, blowup=16, grind=16, min_security_bits=128, trace_mode=AGG_TRACE_VALID):
+def agg_prove(steps, queries=64, blowup=16, grind=16, min_security_bits=128, trace_mode=AGG_TRACE_VALID, *,
+              ctx=None):
     """RecursionPublicBuilder::build_public + RecursionBackend::prove + RecursionArtifactCodec::
-    encode (lib.rs:295-551): ZKLSTP1 step proofs -> (ZKLRC1 artifact, recursion digest)."""
+    encode (lib.rs:295-551): ZKLSTP1 step proofs -> (ZKLRC1 artifact, recursion digest).
+    ctx (a Context): the Poseidon hashing of the child replays runs on its device
+    (zkl_hip_agg_prove) -- same artifact, digest and rejections; None: host threads."""
     lib = load_library()
     arr, lens = _steps_args(steps)
     o = AggOptions(queries, blowup, grind, min_security_bits, trace_mode)
     out, ln, dg = C.POINTER(C.c_uint8)(), C.c_size_t(), (C.c_uint8 * 32)()
-    rc = lib.zkl_agg_prove(arr, lens, len(steps), C.byref(o), C.byref(out), C.byref(ln), dg)
+    if ctx is None:
+        rc = lib.zkl_agg_prove(arr, lens, len(steps), C.byref(o), C.byref(out), C.byref(ln), dg)
+    else:
+        rc = lib.zkl_hip_agg_prove(ctx.ptr, arr, lens, len(steps), C.byref(o), C.byref(out), C.byref(ln), dg)
     if rc:
         raise ZklError(rc, lib.zkl_hip_last_error(None).decode(errors="replace"))
     data = C.string_at(out, ln.value)
     lib.zkl_hip_free(out)
     return data, bytes(dg)
+
+
+AGG_TIME_NAMES = ("replay_host", "replay_hash", "trace", "prove", "grind", "total")
+
+
+def agg_last_times():
+    """Wall times (ms) of this thread's last agg_prove (zkl_agg_last_times), in the order of
+    AGG_TIME_NAMES: child decode + replay on the host, the replay's hashing (host threads or
+    device incl. copies), build_public + aggregation trace, the ZlAggAir proof without its
+    grinding, the grinding, the whole call."""
+    lib = load_library()
+    v = (C.c_double * 6)()
+    k = lib.zkl_agg_last_times(v, 6)
+    return [v[i] for i in range(k)]
 
 
 def agg_verify(artifact: bytes, min_security_bits: int = 128) -> None:
@@ -378,6 +403,37 @@ def verify_segment(proof: bytes, pi: AirPublicInputs, opts: ProofOptions) -> Non
     rc = lib.zkl_verify_segment(bytes(proof), len(proof), C.byref(pi), C.byref(opts))
     if rc != 0:
         raise ZklError(rc, lib.zkl_hip_last_error(None).decode(errors="replace"))
+
+
+VERIFY_MSG_LEN = 160  # ZKL_VERIFY_MSG_LEN
+
+
+def verify_segments(proofs, pis, opts, ctx=None):
+    """verify_segment over a batch (zkl_hip_verify_segments): one message per proof, "" when it
+    verifies, otherwise what verify_segment raises for that proof alone.  ctx (a Context): the
+    Poseidon hashing of the openings and the composition-coefficient draws run on its device;
+    None: host threads.  pis / opts: one AirPublicInputs / ProofOptions per proof."""
+    lib = load_library()
+    n = len(proofs)
+    if len(pis) != n or len(opts) != n:
+        raise ValueError("verify_segments: one AirPublicInputs and one ProofOptions per proof")
+    arr, lens = _steps_args(proofs)
+    pa, oa = (AirPublicInputs * n)(), (ProofOptions * n)()
+    for i in range(n):
+        C.memmove(C.byref(pa, i * C.sizeof(AirPublicInputs)), C.byref(pis[i]), C.sizeof(AirPublicInputs))
+        C.memmove(C.byref(oa, i * C.sizeof(ProofOptions)), C.byref(opts[i]), C.sizeof(ProofOptions))
+    st = (C.c_int32 * n)()
+    msgs = C.create_string_buffer(max(1, n * VERIFY_MSG_LEN))
+    rc = lib.zkl_hip_verify_segments(ctx.ptr if ctx is not None else None, arr, lens, pa, oa, n, st, msgs)
+    if rc:
+        raise ZklError(rc, lib.zkl_hip_last_error(None).decode(errors="replace"))
+    out = []
+    for i in range(n):
+        m = msgs.raw[i * VERIFY_MSG_LEN:(i + 1) * VERIFY_MSG_LEN].split(b"\0", 1)[0].decode(errors="replace")
+        if (st[i] == 0) != (m == ""):
+            raise ZklError(-4, f"verify_segments: status {st[i]} with message {m!r} for proof {i}")
+        out.append(m)
+    return out
 
 
 class row_digest_rule:
