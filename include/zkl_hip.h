@@ -199,6 +199,72 @@ int zkl_hip_last_proof(zkl_ctx* ctx, uint8_t* buf, size_t cap, size_t* len);
 int zkl_hip_check_request(uint32_t width, uint32_t n_rows, const zkl_air_public_inputs* pi,
                           const zkl_proof_options* opts);
 
+/* ---- trace preflight (the reference's preflight.rs:73-440, run from prove.rs:188-212) --------
+ * A trace check on the device that names what is wrong with a trace: the first row (below
+ * n_rows - 1; the last row is the transition exemption) with a non-zero transition constraint
+ * of ZkLispAir, the first such constraint in evaluation order and its value -- what
+ * preflight.rs reports -- or, when every transition holds, the first assertion of the AIR
+ * (Winterfell order) whose trace cell differs, which winterfell's debug `validate` covers.
+ *
+ * The device pass is a filter: a row fails iff sum_j alpha_j c_j != 0 for n_tc coefficients
+ * drawn from hash_elements(pi_elements | [width, n_rows, seed_lo, seed_hi]); the failing row is
+ * then resolved exactly on the host, constraint by constraint.  A row with some c_j != 0 is
+ * missed with probability 2^-128 for a trace fixed independently of `seed` (default 0, so runs
+ * reproduce).  This is a diagnostic, not a soundness argument: a trace built to fit one seed's
+ * coefficients passes the filter under that seed; the proof itself still fails for it.
+ *
+ * The report mirrors PreflightReport (preflight.rs:29-70) without its VmSnap, which keys on
+ * literal constraint indices of one layout, and without the compiler statistics. */
+typedef struct {
+  uint32_t kind;            /* 0 none, 1 transition constraint, 2 assertion */
+  uint32_t index;           /* constraint index, or position in the AIR's assertion order */
+  uint32_t row, pos;        /* failing row; pos = row % 32 */
+  zkl_f128 value;           /* c_index at that row, or the trace cell of a failing assertion */
+  uint32_t column;          /* assertions: the asserted column ... */
+  uint32_t lanes_exp_valid; /* lanes_exp is set (Poseidon block present and index < 27 * 12) */
+  zkl_f128 expected;        /* ... and the asserted value */
+  zkl_f128 g_map, g_final;  /* the schedule gate columns of the row */
+  uint32_t round_gates;     /* bit j: round gate j of the row is 1 (27 bits) */
+  uint32_t ram_valid;       /* ram is set (the layout has RAM columns) */
+  zkl_f128 lanes_cur[4], lanes_next[4]; /* lanes l, r, c0, c1 of the row and the next */
+  zkl_f128 lanes_exp[4];    /* MDS s^3 + rc[index / 12] for those lanes (preflight.rs:204-229) */
+  /* RamSnap: sorted, addr cur/next, clk cur/next, val, is_write, last_write cur/next,
+   * gp_unsorted cur/next, gp_sorted cur/next (preflight.rs:232-250) */
+  zkl_f128 ram[13];
+} zkl_trace_report;
+
+/* Check a trace resident on ctx's device (column-major).  The request's shape checks run first
+ * (n_rows a power of two >= 32, width = the segment layout's, the public-input shape):
+ * ZKL_E_INVALID.  Otherwise ZKL_OK with out->kind = 0 or a finding; a finding is not an error of
+ * the call.  ZKL_E_INTERNAL if the device flags a row in which the host finds no violation. */
+int zkl_hip_check_trace_device(zkl_ctx* ctx, const void* d_trace, uint32_t width, uint32_t n_rows,
+                               const zkl_air_public_inputs* pi, uint64_t seed, zkl_trace_report* out);
+/* The same for a host trace, uploaded whole into a device buffer the context owns. */
+int zkl_hip_check_trace(zkl_ctx* ctx, const zkl_f128* trace, uint32_t width, uint32_t n_rows,
+                        const zkl_air_public_inputs* pi, uint64_t seed, zkl_trace_report* out);
+/* Per context, default off (the reference's PreflightMode::Off).  When on, every
+ * zkl_hip_prove_segment_device* call checks d_trace first (seed 0), and zkl_hip_prove_segment
+ * uploads the host trace whole, checks it and proves from that resident copy (the chunked upload
+ * transforms chunks in place, so it cannot be checked row-wise).  A finding returns
+ * ZKL_E_INVALID with no proof and no LDE work; zkl_hip_last_error is the reference's text with
+ * the value as a decimal integer,
+ *   preflight: constraint 94 non-zero at row 299: 1
+ *   preflight: assertion {k} (column {c}) fails at row {r}: trace {v}, expected {e}
+ * and the report stays readable through zkl_hip_last_trace_report.  Proof bytes are the same
+ * with it on or off. */
+int zkl_hip_set_preflight(zkl_ctx* ctx, int on);
+int zkl_hip_preflight(const zkl_ctx* ctx);
+/* The report of the last check on ctx (either entry point above, or a prove call's preflight);
+ * ZKL_E_INVALID when none was made. */
+int zkl_hip_last_trace_report(zkl_ctx* ctx, zkl_trace_report* out);
+/* Host only, no ctx: the values c_0 .. c_(n_tc - 1) of ZkLispAir's transition constraints on the
+ * frame (cur, next) = rows (row, row + 1) of a width x n_rows trace, row < n_rows - 1, in the
+ * reference's evaluation order.  *n_tc receives their number; values NULL only queries it,
+ * otherwise cap >= *n_tc entries are written.  The preflight's exact resolution step. */
+int zkl_eval_transition_row(uint32_t width, uint32_t n_rows, const zkl_air_public_inputs* pi, uint32_t row,
+                            const zkl_f128* cur, const zkl_f128* next, zkl_f128* values, uint32_t cap,
+                            uint32_t* n_tc);
+
 /* Host-side wall times (ms) of the last proof on ctx: [0] host setup before the first
  * kernel (AIR instance, assertions, uploads), [1] host time between the first and last
  * stage marks not covered by device work, [2] the whole call, [3] the host-trace upload loop

@@ -13,6 +13,9 @@
 //   zkl::AirPublicInputs         crate::AirPublicInputs (lib.rs:75-95), flattened
 //   zkl::ZkProver                ZkProver::new / prove (prove.rs:105-257): one segment proof,
 //                                Proof::to_bytes out (the call at prove.rs:1142)
+//   zkl::PreflightMode / PreflightReport / ZkProver::check   frontend::PreflightMode and
+//                                preflight::run (preflight.rs:29-440): the trace check in front
+//                                of prove (prove.rs:188-212), on the device
 //   zkl::verify_proof            verify_proof (prove.rs:802-941), one segment
 //   zkl::StepProof               proof::step::StepProof::to_bytes / digest (step.rs:79-151,
 //                                digest.rs:16-68), step_meta_for (prove.rs:1103-1174),
@@ -34,6 +37,7 @@
 #include <array>
 #include <cstdint>
 #include <cstring>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -146,6 +150,79 @@ class TraceTable {
   std::vector<BaseElement> d_;
 };
 
+// zk_lisp_proof::frontend::PreflightMode (Off / On; the reference's Console / Json only choose
+// how the report is printed: PreflightReport::to_string / to_json below)
+enum class PreflightMode { Off, On };
+
+namespace detail {
+inline std::string fe_decimal(const BaseElement& v) {
+  unsigned __int128 x = ((unsigned __int128)v.hi << 64) | v.lo;
+  if (!x) return "0";
+  std::string s;
+  for (; x; x /= 10) s.insert(s.begin(), (char)('0' + (int)(x % 10)));
+  return s;
+}
+}  // namespace detail
+
+// PreflightReport (preflight.rs:29-70) over zkl_trace_report; kind 2 (a failing assertion) is this
+// library's addition.  The reference's VmSnap and compiler statistics are not reproduced.
+struct PreflightReport : zkl_trace_report {
+  PreflightReport() { std::memset(static_cast<zkl_trace_report*>(this), 0, sizeof(zkl_trace_report)); }
+  bool is_transition() const { return kind == 1; }
+  bool is_assertion() const { return kind == 2; }
+  bool gates_map() const { return g_map.lo == 1 && g_map.hi == 0; }
+  bool gates_final() const { return g_final.lo == 1 && g_final.hi == 0; }
+  bool round(int j) const { return (round_gates >> j) & 1u; }
+  // the message a prove refused by the preflight carries (prove.rs:207)
+  std::string to_string() const {
+    if (kind == 1)
+      return "preflight: constraint " + std::to_string(index) + " non-zero at row " + std::to_string(row) + ": " +
+             detail::fe_decimal(value);
+    if (kind == 2)
+      return "preflight: assertion " + std::to_string(index) + " (column " + std::to_string(column) + ") fails at row " +
+             std::to_string(row) + ": trace " + detail::fe_decimal(value) + ", expected " + detail::fe_decimal(expected);
+    return "preflight: ok";
+  }
+  // the reference's JSON field names
+  std::string to_json() const {
+    auto q = [](const BaseElement& v) { return "\"" + detail::fe_decimal(v) + "\""; };
+    auto four = [&](const BaseElement* v) { return "[" + q(v[0]) + "," + q(v[1]) + "," + q(v[2]) + "," + q(v[3]) + "]"; };
+    std::string s = "{\"row\":" + std::to_string(row) + ",\"constraint_idx\":" +
+                    (kind == 1 ? std::to_string(index) : std::string("null")) + ",\"constraint_val\":" + q(value) +
+                    ",\"pos\":" + std::to_string(pos) + ",\"gates_map\":" + (gates_map() ? "true" : "false") +
+                    ",\"gates_final\":" + (gates_final() ? "true" : "false") + ",\"rounds\":[";
+    for (int j = 0; j < 27; j++) s += std::string(j ? "," : "") + (round(j) ? "true" : "false");
+    s += "],\"lanes_cur\":" + four(lanes_cur) + ",\"lanes_next\":" + four(lanes_next) +
+         ",\"lanes_exp\":" + (lanes_exp_valid ? four(lanes_exp) : std::string("null")) + ",\"ram\":";
+    if (ram_valid) {
+      static const char* const names[13] = {"sorted", "addr_cur", "addr_next", "clk_cur", "clk_next", "val", "is_write",
+                                            "last_cur", "last_next", "gp_unsorted_cur", "gp_unsorted_next",
+                                            "gp_sorted_cur", "gp_sorted_next"};
+      s += std::string("{\"sorted\":") + (ram[0].lo == 1 && ram[0].hi == 0 ? "true" : "false");
+      for (int k = 1; k < 13; k++) s += std::string(",\"") + names[k] + "\":" + q(ram[k]);
+      s += "}";
+    } else {
+      s += "null";
+    }
+    s += ",\"vm\":null,\"peak_live\":null";
+    if (kind == 2)
+      s += ",\"assertion_idx\":" + std::to_string(index) + ",\"column\":" + std::to_string(column) + ",\"expected\":" +
+           q(expected);
+    return s + "}";
+  }
+};
+
+// The values of ZkLispAir's transition constraints on rows (row, row + 1) of `trace`, in the
+// reference's evaluation order (zkl_eval_transition_row; host only, no Device)
+inline std::vector<BaseElement> eval_transition_row(uint32_t width, uint32_t length, const zkl_air_public_inputs& pi,
+                                                    uint32_t row, const BaseElement* cur, const BaseElement* next) {
+  uint32_t n_tc = 0;
+  detail::check(zkl_eval_transition_row(width, length, &pi, row, cur, next, nullptr, 0, &n_tc));
+  std::vector<BaseElement> v(n_tc);
+  detail::check(zkl_eval_transition_row(width, length, &pi, row, cur, next, v.data(), n_tc, &n_tc));
+  return v;
+}
+
 // One device context (streams, buffers, tables); the reference's rayon pool calls prove_segment
 // from several threads: use one Device per thread and device (calls on one Device serialise).
 class Device {
@@ -167,6 +244,20 @@ class Device {
     int n = 0;
     detail::check(zkl_hip_device_count(&n));
     return n;
+  }
+  // frontend::PreflightMode of every prove on this Device (the reference's with_preflight_mode,
+  // prove.rs:188-212); the flag lives in the device context, not in a prover: two provers may
+  // share a Device
+  void set_preflight_mode(PreflightMode m) {
+    detail::check(zkl_hip_set_preflight(ctx_, m == PreflightMode::On ? 1 : 0), ctx_);
+  }
+  PreflightMode preflight_mode() const { return zkl_hip_preflight(ctx_) ? PreflightMode::On : PreflightMode::Off; }
+  // the finding of the last check on this Device (a prove refused by the preflight included)
+  std::optional<PreflightReport> last_report() const {
+    PreflightReport r;
+    detail::check(zkl_hip_last_trace_report(ctx_, &r), ctx_);
+    if (r.kind == 0) return std::nullopt;
+    return r;
   }
 
  private:
@@ -230,6 +321,24 @@ class ZkProver {
       detail::check(rc, dev_->ctx());
     }
     out.resize(len);
+  }
+  // preflight::run (preflight.rs:73-440) on the device without proving: nullopt when every
+  // transition constraint and assertion of this prover's AIR holds on `trace`, else the first
+  // finding.  `seed` picks the filter's check coefficients (zkl_hip.h).  Whether prove() runs it
+  // first is the Device's PreflightMode, not a flag of the prover.
+  std::optional<PreflightReport> check(const TraceTable& trace, uint64_t seed = 0) const {
+    PreflightReport r;
+    detail::check(zkl_hip_check_trace(dev_->ctx(), trace.data(), trace.width(), trace.length(), &pi_, seed, &r),
+                  dev_->ctx());
+    if (r.kind == 0) return std::nullopt;
+    return r;
+  }
+  std::optional<PreflightReport> check_device(const void* d_trace, uint32_t width, uint32_t length,
+                                              uint64_t seed = 0) const {
+    PreflightReport r;
+    detail::check(zkl_hip_check_trace_device(dev_->ctx(), d_trace, width, length, &pi_, seed, &r), dev_->ctx());
+    if (r.kind == 0) return std::nullopt;
+    return r;
   }
   const ProofOptions& options() const { return opts_; }
 

@@ -279,6 +279,17 @@ void launch_constraint_eval(const fe* d_lde, const fe* d_roots, size_t Ntab, con
                             const DerivedConsts* dD, bool pose_block, bool ram_merkle,
                             fe* d_xinv /* ce entries: 1 / (x_i - g^(n-1)) */, bool xinv_ready, fe* d_out,
                             hipStream_t s, int split = 0, fe* d_pose_part /* ce entries, Poseidon layouts */ = nullptr);
+// Trace preflight: the transition sum of rows (k, k + 1), k < n - 1, of the
+// caller's column-major n-row trace d_trace, under the check coefficients in dK->alpha (with
+// dD->pose_k / dD->apre from launch_pose_k) and the AIR in dK->air; d_rowper: 32 x 31 selector
+// values of row k mod 32.  *d_min = the smallest row whose sum is non-zero, 0xFFFFFFFF when none.
+// Poseidon layouts run the block in a kernel of its own through d_pose_part (n entries).
+void launch_check_rows(const fe* d_trace, size_t n, const fe* d_rowper, const ProofConsts* dK, const DerivedConsts* dD,
+                       bool pose_block, bool ram_merkle, fe* d_pose_part, uint32_t* d_min, hipStream_t s);
+// *d_min = the smallest a < n_assert with trace[col[a] * n + step[a]] != val[a], 0xFFFFFFFF when
+// none.  The caller bounds col and step against the trace.
+void launch_check_assertions(const fe* d_trace, size_t n, const uint32_t* d_col, const uint32_t* d_step,
+                             const fe* d_val, size_t n_assert, uint32_t* d_min, hipStream_t s);
 // boundary vectors: vec[slot*n + step] = beta_a ; wv[s] = sum beta_a*value_a over assertions at step s
 void launch_boundary_scatter(const uint32_t* d_slot, const uint32_t* d_step, const fe* d_beta, size_t n_assert,
                              size_t n, fe* d_vecs, hipStream_t s);

@@ -1233,6 +1233,102 @@ void launch_constraint_eval(const fe* d_lde, const fe* d_roots, size_t Ntab, con
     constraint_eval_kernel<false><<<grid, 256, 0, s>>>(d_lde, d_roots, shift, d_pertab, d_bm, dK, dD, d_xinv, d_out, split);
 }
 
+// ---- trace preflight: the evaluator on the trace domain --------------------
+// Thread k < n - 1 is row k of the caller's column-major trace (no LDE, no split layout): cur /
+// nxt are rows k and k + 1, per the 0/1 selector values of row k mod 32 (rowper: 32 x 31),
+// p_last = 0 (row n - 1 is the transition exemption and is not evaluated), no boundary terms and
+// no division.  K->alpha holds the check coefficients: a row fails when sum_j alpha_j c_j != 0.
+// The smallest failing row goes to *d_min (cleared to 0xFFFFFFFF by the launch): minimum inside
+// the wave, then one atomicMin per wave that saw a failure.
+__device__ __forceinline__ void wave_min_to(uint32_t v, uint32_t* __restrict__ d_min) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
+  if ((threadIdx.x & 63) == 0 && v != 0xFFFFFFFFu) atomicMin(d_min, v);
+}
+template <bool POSE, bool RM, int PART>
+__device__ __forceinline__ void constraint_rows_body(const fe* __restrict__ trace, size_t n,
+                                                     const fe* __restrict__ rowper,
+                                                     const ProofConsts* __restrict__ K,
+                                                     const DerivedConsts* __restrict__ D, fe* __restrict__ pose_part,
+                                                     uint32_t* __restrict__ d_min) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t bad = 0xFFFFFFFFu;
+  if (k + 1 < n) {
+    auto cur = [&](int c) { return trace[(size_t)c * n + k]; };
+    auto nxt = [&](int c) { return trace[(size_t)c * n + k + 1]; };
+    const fe* per = rowper + (k & 31) * 31;
+    fe sum = air_transition_sum<POSE, RM, PART>(K->air, cur, nxt, per, fe_zero(), K->alpha, D->pose_k, D->apre);
+    if (PART == 1) {
+      pose_part[k] = sum;
+      return;
+    }
+    if (PART == 2) sum = fe_add(sum, pose_part[k]);
+    if (!fe_is_zero(sum)) bad = (uint32_t)k;
+  }
+  if (PART != 1) wave_min_to(bad, d_min);
+}
+// No occupancy attribute: one evaluator pass over n points (the composition does 8 n), not worth
+// spills.  The names carry the evaluator family names of tests/test_abi.py's scratch list.
+template <bool RM>
+__global__ __launch_bounds__(256) void constraint_eval_kernel_rows(const fe* __restrict__ trace, size_t n,
+                                                                   const fe* __restrict__ rowper,
+                                                                   const ProofConsts* __restrict__ K,
+                                                                   const DerivedConsts* __restrict__ D,
+                                                                   uint32_t* __restrict__ d_min) {
+  constraint_rows_body<false, RM, 0>(trace, n, rowper, K, D, nullptr, d_min);
+}
+__global__ __launch_bounds__(256) void constraint_eval_pose_part_kernel_rows(const fe* __restrict__ trace, size_t n,
+                                                                             const fe* __restrict__ rowper,
+                                                                             const ProofConsts* __restrict__ K,
+                                                                             const DerivedConsts* __restrict__ D,
+                                                                             fe* __restrict__ pose_part) {
+  constraint_rows_body<true, false, 1>(trace, n, rowper, K, D, pose_part, nullptr);
+}
+template <bool RM>
+__global__ __launch_bounds__(256) void constraint_eval_pose_kernel_rows(const fe* __restrict__ trace, size_t n,
+                                                                        const fe* __restrict__ rowper,
+                                                                        const ProofConsts* __restrict__ K,
+                                                                        const DerivedConsts* __restrict__ D,
+                                                                        fe* __restrict__ pose_part,
+                                                                        uint32_t* __restrict__ d_min) {
+  constraint_rows_body<true, RM, 2>(trace, n, rowper, K, D, pose_part, d_min);
+}
+// one thread per assertion (col, step, value): the smallest index whose trace cell differs
+__global__ __launch_bounds__(256) void check_assertions_kernel(const fe* __restrict__ trace, size_t n,
+                                                               const uint32_t* __restrict__ col,
+                                                               const uint32_t* __restrict__ step,
+                                                               const fe* __restrict__ val, size_t na,
+                                                               uint32_t* __restrict__ d_min) {
+  const size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t bad = 0xFFFFFFFFu;
+  if (a < na && !fe_eq(trace[(size_t)col[a] * n + step[a]], val[a])) bad = (uint32_t)a;
+  wave_min_to(bad, d_min);
+}
+
+void launch_check_rows(const fe* d_trace, size_t n, const fe* d_rowper, const ProofConsts* dK, const DerivedConsts* dD,
+                       bool pose_block, bool ram_merkle, fe* d_pose_part, uint32_t* d_min, hipStream_t s) {
+  if (n < 2 || n > 0x80000000ull) throw std::invalid_argument("launch_check_rows: 2 <= n <= 2^31 rows");
+  if (pose_block && !d_pose_part) throw std::invalid_argument("launch_check_rows: Poseidon layout needs the pose_part buffer");
+  ZKL_HIPCHECK(hipMemsetAsync(d_min, 0xFF, sizeof(uint32_t), s));
+  const unsigned grid = (unsigned)((n - 1 + 255) / 256);
+  if (pose_block)
+    constraint_eval_pose_part_kernel_rows<<<grid, 256, 0, s>>>(d_trace, n, d_rowper, dK, dD, d_pose_part);
+  if (pose_block && ram_merkle)
+    constraint_eval_pose_kernel_rows<true><<<grid, 256, 0, s>>>(d_trace, n, d_rowper, dK, dD, d_pose_part, d_min);
+  else if (pose_block)
+    constraint_eval_pose_kernel_rows<false><<<grid, 256, 0, s>>>(d_trace, n, d_rowper, dK, dD, d_pose_part, d_min);
+  else if (ram_merkle)
+    constraint_eval_kernel_rows<true><<<grid, 256, 0, s>>>(d_trace, n, d_rowper, dK, dD, d_min);
+  else
+    constraint_eval_kernel_rows<false><<<grid, 256, 0, s>>>(d_trace, n, d_rowper, dK, dD, d_min);
+}
+void launch_check_assertions(const fe* d_trace, size_t n, const uint32_t* d_col, const uint32_t* d_step,
+                             const fe* d_val, size_t na, uint32_t* d_min, hipStream_t s) {
+  if (na >= 0xFFFFFFFFull) throw std::invalid_argument("launch_check_assertions: too many assertions");
+  ZKL_HIPCHECK(hipMemsetAsync(d_min, 0xFF, sizeof(uint32_t), s));
+  if (na) check_assertions_kernel<<<(unsigned)((na + 255) / 256), 256, 0, s>>>(d_trace, n, d_col, d_step, d_val, na, d_min);
+}
+
 __global__ void boundary_scatter_kernel(const uint32_t* slot, const uint32_t* step, const fe* beta, size_t na, size_t n,
                                         fe* vecs) {
   size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

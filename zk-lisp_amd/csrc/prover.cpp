@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "lde_plan.h"
 #include "host_proof.h"
+#include "preflight.h"
 #include "proof_view.h"
 
 using namespace zkl;
@@ -178,6 +179,12 @@ struct zkl_ctx {
   // (inputs, then computed digests), the job lists, and their pinned staging
   DBuf vbuf, vjobs;
   HBuf h_vin, h_vout;
+  // trace preflight: off by default; the selector table of the trace domain, the
+  // assertion lists, the two result words, their pinned staging, and the last report
+  bool preflight = false, have_report = false, pf_rowper_ready = false;
+  DBuf pf_rowper, pf_col, pf_step, pf_val, pf_min;
+  HBuf h_pf;
+  zkl_trace_report report{};
 };
 
 static const char* kFamilyNames =
@@ -1244,6 +1251,167 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   }
 }
 
+// ====================================================================== trace preflight
+// The shape checks of a request that has no proof options (zkl_hip_check_trace*).
+void validate_trace_shape(uint32_t W, uint32_t n32, const zkl_air_public_inputs& pi) {
+  const size_t n = n32;
+  if (n < 32 || (n & (n - 1))) throw InvalidArg("trace length must be a power of two >= 32");
+  if (pi.n_main_slots > ZKL_MAX_MAIN_SLOTS) throw InvalidArg("n_main_slots exceeds ZKL_MAX_MAIN_SLOTS");
+  if (W == 0 || W > 4096) throw InvalidArg("trace width must be in 1..4096");
+}
+
+// Filter on the device, resolve on the host.  One round trip when the trace is
+// valid: the transition pass and the assertion pass are queued together and their two result
+// words read back at once; a failing transition takes precedence over any assertion, as in the
+// oracle (oracle/api.c:81-86).  On a finding the two rows come back through launch_gather.
+// The report is left in C->report; caller holds C->mu.
+void check_trace_impl(zkl_ctx* C, const fe* d_trace, uint32_t W, uint32_t n32, const zkl_air_public_inputs& pi,
+                      uint64_t seed) {
+  const auto t_call0 = std::chrono::steady_clock::now();
+  hipStream_t s = C->stream;
+  const size_t n = n32;
+  C->have_report = false;
+  zkl_trace_report& rep = C->report;
+  memset(&rep, 0, sizeof rep);
+  validate_trace_shape(W, n32, pi);
+  AirInstance& air = C->air;
+  {
+    const std::string e = build_air(pi, W, n, air);
+    if (!e.empty()) throw InvalidArg(e);
+  }
+  HT("pf_air_built");
+  const int n_tc = air.n_tc;
+  if (n_tc < 0 || n_tc > 1024) throw InvalidArg("more than 1024 transition constraints");
+  const size_t na = air.assertions.size();
+  for (const Assertion& a : air.assertions)  // the kernels index the trace with these
+    if (a.col >= W || a.step >= n) throw std::runtime_error("internal: assertion outside the trace");
+
+  // pinned staging: alphas | assertion values | gathered rows | gather addresses | columns | steps | result words
+  const size_t off_val = (size_t)1024 * sizeof(fe), off_rows = off_val + na * sizeof(fe),
+               off_addr = off_rows + 2 * (size_t)W * sizeof(fe), off_col = off_addr + 2 * (size_t)W * 8,
+               off_step = off_col + na * 4, off_min = (off_step + na * 4 + 15) & ~(size_t)15;
+  C->h_pf.ensure(off_min + 16);
+  fe* h_alpha = C->h_pf.at<fe>(0);
+  fe* h_val = C->h_pf.at<fe>(off_val);
+  fe* h_rows = C->h_pf.at<fe>(off_rows);
+  uint64_t* h_addr = C->h_pf.at<uint64_t>(off_addr);
+  uint32_t* h_col = C->h_pf.at<uint32_t>(off_col);
+  uint32_t* h_step = C->h_pf.at<uint32_t>(off_step);
+  uint32_t* h_min = C->h_pf.at<uint32_t>(off_min);
+  {
+    const std::vector<fe> al = preflight_alphas(pi, W, n, seed, n_tc);
+    std::copy(al.begin(), al.end(), h_alpha);
+  }
+  for (size_t k = 0; k < na; k++) {
+    h_col[k] = air.assertions[k].col;
+    h_step[k] = air.assertions[k].step;
+    h_val[k] = air.assertions[k].value;
+  }
+  HT("pf_staged");
+  if (!C->pf_rowper_ready) {
+    const std::vector<fe> tab = row_selector_table();
+    C->pf_rowper.ensure(tab.size() * sizeof(fe));
+    HIPCHECK(hipMemcpyAsync(C->pf_rowper.p, tab.data(), tab.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    C->pf_rowper_ready = true;
+  }
+  C->kconst.ensure(sizeof(ProofConsts));
+  ProofConsts* dK = (ProofConsts*)C->kconst.p;
+  C->dconst.ensure(sizeof(DerivedConsts));
+  DerivedConsts* dD = (DerivedConsts*)C->dconst.p;
+  C->h_air.ensure(sizeof(AirDevice));
+  memcpy(C->h_air.p, &air.dev, sizeof(AirDevice));
+  C->pf_min.ensure(2 * sizeof(uint32_t));
+  C->pf_col.ensure(std::max<size_t>(na, 1) * 4);
+  C->pf_step.ensure(std::max<size_t>(na, 1) * 4);
+  C->pf_val.ensure(std::max<size_t>(na, 1) * sizeof(fe));
+  const bool pose = air.dev.pose_block != 0, rm = (air.dev.ram_block | air.dev.merkle_block) != 0;
+  if (pose) C->posep.ensure(n * sizeof(fe));
+  uint32_t* d_min = (uint32_t*)C->pf_min.p;
+
+  upload_air_consts(dK, *C->h_air.at<AirDevice>(), s);
+  HIPCHECK(hipMemcpyAsync(dK->alpha, h_alpha, sizeof(fe) * (size_t)n_tc, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(C->pf_col.p, h_col, na * 4, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(C->pf_step.p, h_step, na * 4, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(C->pf_val.p, h_val, na * sizeof(fe), hipMemcpyHostToDevice, s));
+  {
+    KScope k(C, KF_MISC);
+    launch_pose_k(dK, dD, n_tc, pose, s);
+    launch_check_rows(d_trace, n, C->pf_rowper.f(), dK, dD, pose, rm, pose ? C->posep.f() : nullptr, d_min, s);
+    launch_check_assertions(d_trace, n, (const uint32_t*)C->pf_col.p, (const uint32_t*)C->pf_step.p, C->pf_val.f(), na,
+                            d_min + 1, s);
+  }
+  check_launch("trace preflight");
+  HT("pf_queued");
+  HIPCHECK(hipMemcpyAsync(h_min, d_min, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  HT("pf_verdict");
+  // with every family timed, zkl_hip_kernel_times' "misc" is this check's device time (until the
+  // next proof resolves its own marks)
+  if (C->ktiming == 2) resolve_kernel_times(C);
+  const uint32_t bad_row = h_min[0], bad_as = h_min[1];
+  if (bad_row == 0xFFFFFFFFu && bad_as == 0xFFFFFFFFu) {
+    C->have_report = true;
+    return;
+  }
+  if (bad_row != 0xFFFFFFFFu && (size_t)bad_row + 1 >= n) throw std::runtime_error("internal: preflight row out of range");
+  if (bad_row == 0xFFFFFFFFu && bad_as >= na) throw std::runtime_error("internal: preflight assertion out of range");
+  // rows r and r + 1 (an assertion on the last row: that row twice, as preflight.rs:166 frames it)
+  const size_t r = bad_row != 0xFFFFFFFFu ? bad_row : air.assertions[bad_as].step;
+  const size_t r1 = r + 1 < n ? r + 1 : r;
+  for (uint32_t c = 0; c < W; c++) {
+    h_addr[c] = (uint64_t)(uintptr_t)(d_trace + (size_t)c * n + r);
+    h_addr[W + c] = (uint64_t)(uintptr_t)(d_trace + (size_t)c * n + r1);
+  }
+  C->gaddr.ensure(2 * (size_t)W * 8);
+  C->gout.ensure(2 * (size_t)W * sizeof(fe));
+  HIPCHECK(hipMemcpyAsync(C->gaddr.p, h_addr, 2 * (size_t)W * 8, hipMemcpyHostToDevice, s));
+  launch_gather((const uint64_t*)C->gaddr.p, 2 * (size_t)W, C->gout.f(), s);
+  check_launch("preflight row fetch");
+  HIPCHECK(hipMemcpyAsync(h_rows, C->gout.p, 2 * (size_t)W * sizeof(fe), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const fe *cur = h_rows, *nxt = h_rows + W;
+  rep.row = (uint32_t)r;
+  if (bad_row != 0xFFFFFFFFu) {
+    const std::vector<fe> v = eval_transition_row(air, r, cur, nxt);
+    size_t i = 0;
+    while (i < v.size() && fe_is_zero(v[i])) i++;
+    if (i == v.size())  // never a verdict from the filter alone
+      throw std::runtime_error("preflight: device flagged row " + std::to_string(r) + ", host finds no violation");
+    rep.kind = 1;
+    rep.index = (uint32_t)i;
+    rep.value = to_abi(v[i]);
+  } else {
+    const Assertion& a = air.assertions[bad_as];
+    if (fe_eq(cur[a.col], a.value))
+      throw std::runtime_error("preflight: device flagged assertion " + std::to_string(bad_as) + ", host finds no violation");
+    rep.kind = 2;
+    rep.index = bad_as;
+    rep.column = a.col;
+    rep.value = to_abi(cur[a.col]);
+    rep.expected = to_abi(a.value);
+  }
+  fill_report_row(air, W, cur, nxt, rep);
+  C->have_report = true;
+}
+
+// the opt-in step in front of a proof: a finding is the proof call's ZKL_E_INVALID
+void preflight_or_throw(zkl_ctx* C, const fe* d_trace, uint32_t W, uint32_t n32, const zkl_air_public_inputs& pi,
+                        const zkl_proof_options& o) {
+  validate_request(W, n32, pi, o);
+  check_trace_impl(C, d_trace, W, n32, pi, 0);
+  if (C->report.kind) throw InvalidArg(report_message(C->report));
+}
+
+// the host trace whole into the context's resident copy
+const fe* upload_trace_whole(zkl_ctx* C, const zkl_f128* trace, uint32_t W, uint32_t n32) {
+  const size_t bytes = (size_t)W * n32 * sizeof(fe);
+  C->trace.ensure(bytes);
+  HIPCHECK(hipMemcpyAsync(C->trace.p, trace, bytes, hipMemcpyHostToDevice, C->stream));
+  HIPCHECK(hipStreamSynchronize(C->stream));  // the caller's memory is pageable: read before we return to it
+  return C->trace.f();
+}
+
 int run_guarded(zkl_ctx* ctx, const std::function<void()>& f) {
   try {
     f();
@@ -1522,6 +1690,13 @@ int zkl_hip_prove_segment(zkl_ctx* c, const zkl_f128* trace, uint32_t width, uin
   c->proof_s.clear();
   int rc = run_guarded(c, [&] {
     HIPCHECK(hipSetDevice(c->device));
+    if (c->preflight) {  // whole upload, check, then prove from the resident copy
+      validate_request(width, n, *pi, *o);
+      const fe* d = upload_trace_whole(c, trace, width, n);
+      preflight_or_throw(c, d, width, n, *pi, *o);
+      prove_impl(c, d, false, width, n, *pi, *o);
+      return;
+    }
     prove_impl(c, trace, true, width, n, *pi, *o);
   });
   return rc ? rc : finish_proof(c->proof_s, proof, len);
@@ -1535,6 +1710,7 @@ int zkl_hip_prove_segment_device(zkl_ctx* c, const void* d_trace, uint32_t width
   c->proof_s.clear();
   int rc = run_guarded(c, [&] {
     HIPCHECK(hipSetDevice(c->device));
+    if (c->preflight) preflight_or_throw(c, (const fe*)d_trace, width, n, *pi, *o);
     prove_impl(c, d_trace, false, width, n, *pi, *o);
   });
   return rc ? rc : finish_proof(c->proof_s, proof, len);
@@ -1571,9 +1747,58 @@ int zkl_hip_prove_segment_device_into(zkl_ctx* c, const void* d_trace, uint32_t 
   c->proof_s.clear();
   int rc = run_guarded(c, [&] {
     HIPCHECK(hipSetDevice(c->device));
+    if (c->preflight) preflight_or_throw(c, (const fe*)d_trace, width, n, *pi, *o);
     prove_impl(c, d_trace, false, width, n, *pi, *o);
   });
   return rc ? rc : copy_last_proof(c, buf, cap, len);
+}
+
+int zkl_hip_check_trace_device(zkl_ctx* c, const void* d_trace, uint32_t width, uint32_t n,
+                               const zkl_air_public_inputs* pi, uint64_t seed, zkl_trace_report* out) {
+  if (!c || !d_trace || !pi || !out) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  memset(out, 0, sizeof *out);
+  int rc = run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    check_trace_impl(c, (const fe*)d_trace, width, n, *pi, seed);
+  });
+  if (!rc) *out = c->report;
+  return rc;
+}
+
+int zkl_hip_check_trace(zkl_ctx* c, const zkl_f128* trace, uint32_t width, uint32_t n, const zkl_air_public_inputs* pi,
+                        uint64_t seed, zkl_trace_report* out) {
+  if (!c || !trace || !pi || !out) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  memset(out, 0, sizeof *out);
+  int rc = run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    c->have_report = false;
+    validate_trace_shape(width, n, *pi);
+    check_trace_impl(c, upload_trace_whole(c, trace, width, n), width, n, *pi, seed);
+  });
+  if (!rc) *out = c->report;
+  return rc;
+}
+
+int zkl_hip_set_preflight(zkl_ctx* c, int on) {
+  if (!c || (on != 0 && on != 1)) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->preflight = on != 0;
+  return ZKL_OK;
+}
+
+int zkl_hip_preflight(const zkl_ctx* c) { return c && c->preflight ? 1 : 0; }
+
+int zkl_hip_last_trace_report(zkl_ctx* c, zkl_trace_report* out) {
+  if (!c || !out) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->have_report) {
+    c->err = "no trace report on this context (no check was made, or the last one failed)";
+    return ZKL_E_INVALID;
+  }
+  *out = c->report;
+  return ZKL_OK;
 }
 
 int zkl_hip_check_request(uint32_t width, uint32_t n_rows, const zkl_air_public_inputs* pi,

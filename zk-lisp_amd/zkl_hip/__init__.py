@@ -106,6 +106,58 @@ class StepInfo(C.Structure):
     ]
 
 
+def _fe_int(v) -> int:
+    return v.lo | (v.hi << 64)
+
+
+RAM_SNAP_FIELDS = ("sorted", "addr_cur", "addr_next", "clk_cur", "clk_next", "val", "is_write", "last_cur", "last_next",
+                   "gp_unsorted_cur", "gp_unsorted_next", "gp_sorted_cur", "gp_sorted_next")
+
+
+class TraceReport(C.Structure):
+    """zkl_trace_report: what the trace preflight found (the reference's PreflightReport,
+    preflight.rs:29-70, plus the assertion form).  kind 1 = transition constraint `index` is
+    non-zero at `row`, kind 2 = assertion `index` (on `column`, value `expected`) fails at `row`."""
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("pos", C.c_uint32),
+                ("value", F128), ("column", C.c_uint32), ("lanes_exp_valid", C.c_uint32), ("expected", F128),
+                ("g_map", F128), ("g_final", F128), ("round_gates", C.c_uint32), ("ram_valid", C.c_uint32),
+                ("lanes_cur", F128 * 4), ("lanes_next", F128 * 4), ("lanes_exp", F128 * 4), ("ram", F128 * 13)]
+
+    @property
+    def value_int(self) -> int:
+        return _fe_int(self.value)
+
+    @property
+    def expected_int(self) -> int:
+        return _fe_int(self.expected)
+
+    def to_json(self) -> dict:
+        """The reference's JSON field names (serde of PreflightReport; field elements as decimal
+        strings); an assertion finding adds assertion_idx / column / expected."""
+        s = lambda v: str(_fe_int(v))  # noqa: E731
+        d = {"row": self.row, "constraint_idx": self.index if self.kind == 1 else None,
+             "constraint_val": s(self.value), "pos": self.pos,
+             "gates_map": _fe_int(self.g_map) == 1, "gates_final": _fe_int(self.g_final) == 1,
+             "rounds": [bool(self.round_gates >> j & 1) for j in range(27)],
+             "lanes_cur": [s(v) for v in self.lanes_cur], "lanes_next": [s(v) for v in self.lanes_next],
+             "lanes_exp": [s(v) for v in self.lanes_exp] if self.lanes_exp_valid else None,
+             "ram": None, "vm": None, "peak_live": None}
+        if self.ram_valid:
+            d["ram"] = {k: s(v) for k, v in zip(RAM_SNAP_FIELDS, self.ram)}
+            d["ram"]["sorted"] = _fe_int(self.ram[0]) == 1
+        if self.kind == 2:
+            d.update(assertion_idx=self.index, column=self.column, expected=s(self.expected))
+        return d
+
+    def __str__(self) -> str:
+        if self.kind == 1:
+            return f"preflight: constraint {self.index} non-zero at row {self.row}: {self.value_int}"
+        if self.kind == 2:
+            return (f"preflight: assertion {self.index} (column {self.column}) fails at row {self.row}: "
+                    f"trace {self.value_int}, expected {self.expected_int}")
+        return "preflight: ok"
+
+
 _lib = None
 
 
@@ -196,6 +248,14 @@ def load_library():
     lib.zkl_agg_trace.argtypes = [P(C.c_char_p), P(C.c_size_t), C.c_uint32, C.c_void_p, C.c_uint32, P(C.c_uint32)]
     lib.zkl_agg_trace_mode.argtypes = [P(C.c_char_p), P(C.c_size_t), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                        P(C.c_uint32)]
+    lib.zkl_hip_check_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(AirPublicInputs), C.c_uint64,
+                                        P(TraceReport)]
+    lib.zkl_hip_check_trace_device.argtypes = lib.zkl_hip_check_trace.argtypes
+    lib.zkl_hip_set_preflight.argtypes = [C.c_void_p, C.c_int]
+    lib.zkl_hip_preflight.argtypes = [C.c_void_p]
+    lib.zkl_hip_last_trace_report.argtypes = [C.c_void_p, P(TraceReport)]
+    lib.zkl_eval_transition_row.argtypes = [C.c_uint32, C.c_uint32, P(AirPublicInputs), C.c_uint32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32)]
     lib.zkl_comm_unique_id.argtypes = [C.c_void_p]
     lib.zkl_comm_available.argtypes = []
     lib.zkl_comm_init.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, P(C.c_void_p)]
@@ -394,6 +454,28 @@ def check_request(width: int, n_rows: int, pi: AirPublicInputs, opts: ProofOptio
     rc = lib.zkl_hip_check_request(width, n_rows, C.byref(pi), C.byref(opts))
     if rc != 0:
         raise ZklError(rc, lib.zkl_hip_last_error(None).decode(errors="replace"))
+
+
+def eval_transition_row(width: int, n_rows: int, pi: AirPublicInputs, row: int, cur, nxt):
+    """The values of ZkLispAir's transition constraints on the frame (cur, nxt) = rows (row,
+    row + 1) of a width x n_rows trace, in the reference's evaluation order, as Python ints
+    (zkl_eval_transition_row; host only).  cur / nxt: `width` F128 each."""
+    lib = load_library()
+    n_tc = C.c_uint32()
+    cur = (F128 * width)(*cur) if not isinstance(cur, C.Array) else cur
+    nxt = (F128 * width)(*nxt) if not isinstance(nxt, C.Array) else nxt
+    rc = lib.zkl_eval_transition_row(width, n_rows, C.byref(pi), row, cur, nxt, None, 0, C.byref(n_tc))
+    if rc == 0:
+        vals = (F128 * n_tc.value)()
+        rc = lib.zkl_eval_transition_row(width, n_rows, C.byref(pi), row, cur, nxt, vals, n_tc.value, C.byref(n_tc))
+    if rc != 0:
+        raise ZklError(rc, lib.zkl_hip_last_error(None).decode(errors="replace"))
+    return [_fe_int(v) for v in vals]
+
+
+def trace_row(trace, width: int, n_rows: int, row: int):
+    """Row `row` of a column-major trace as a (F128 * width) array."""
+    return (F128 * width)(*[F128(trace[c * n_rows + row].lo, trace[c * n_rows + row].hi) for c in range(width)])
 
 
 def verify_segment(proof: bytes, pi: AirPublicInputs, opts: ProofOptions) -> None:
@@ -755,6 +837,42 @@ class Context:
         if rc:
             self._err(rc)
         return bytes(buf)
+
+    # trace preflight (zkl_hip_check_trace*)
+    def _report(self, rc, rep):
+        if rc:
+            self._err(rc)
+        return rep if rep.kind else None
+
+    def check_trace(self, trace, width: int, n_rows: int, pi: AirPublicInputs, seed: int = 0):
+        """Check a host trace on the device: None when every transition constraint and assertion
+        holds, else a TraceReport naming the first failing row and constraint (or assertion)."""
+        rep = TraceReport()
+        ptr = trace if isinstance(trace, int) else C.cast(trace, C.c_void_p)
+        return self._report(self.lib.zkl_hip_check_trace(self.ptr, ptr, width, n_rows, C.byref(pi), seed,
+                                                         C.byref(rep)), rep)
+
+    def check_trace_device(self, d_trace_ptr: int, width: int, n_rows: int, pi: AirPublicInputs, seed: int = 0):
+        """The same for a trace resident in HBM (device pointer)."""
+        rep = TraceReport()
+        return self._report(self.lib.zkl_hip_check_trace_device(self.ptr, C.c_void_p(d_trace_ptr), width, n_rows,
+                                                                C.byref(pi), seed, C.byref(rep)), rep)
+
+    def set_preflight(self, on: bool):
+        """Run the check in front of every prove_segment* call on this context (default off); a
+        finding raises ZklError (invalid) with the reference's message and no proof is made."""
+        rc = self.lib.zkl_hip_set_preflight(self.ptr, 1 if on else 0)
+        if rc:
+            self._err(rc)
+
+    @property
+    def preflight(self) -> bool:
+        return bool(self.lib.zkl_hip_preflight(self.ptr))
+
+    def last_trace_report(self):
+        """The report of the last check on this context (None: that trace was valid)."""
+        rep = TraceReport()
+        return self._report(self.lib.zkl_hip_last_trace_report(self.ptr, C.byref(rep)), rep)
 
     def stage_times(self):
         arr = (C.c_double * len(STAGE_NAMES))()

@@ -28,15 +28,21 @@ class SegmentProof:
 
 
 def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, builders: int = 8, segments=None,
-                  queries: int = 64, blowup: int = 16, grind: int = 16, contexts=None, on_proof=None):
+                  queries: int = 64, blowup: int = 16, grind: int = 16, contexts=None, on_proof=None,
+                  preflight: bool = False):
     """Proves the segments of `plan` ([(r_start, r_end)], zkl_plan_segments) whose indices are in
     `segments` (default all): returns {index: SegmentProof}.  `contexts` may pass existing
     Contexts (then `inflight` = their count and they stay open).  on_proof(SegmentProof) runs in
-    the proving thread after each proof."""
+    the proving thread after each proof.  preflight=True checks every segment's trace on the device
+    before its proof (Context.set_preflight, on the contexts created here): a trace that violates the
+    AIR raises ZklError naming the constraint and row instead of "degree too large"."""
     idx = list(range(len(plan))) if segments is None else list(segments)
     own = contexts is None
     ctxs = [Context(device) for _ in range(inflight)] if own else list(contexts)
     inflight = len(ctxs)
+    if own and preflight:
+        for c in ctxs:
+            c.set_preflight(True)
     # both buffer slots of every context sized once for the widest, longest segment (the full
     # trace's width bounds every segment layout): the builders then never wait on a context
     # that is proving
