@@ -365,6 +365,19 @@ int zkl_hip_scan_columns(zkl_ctx* ctx, const void* d_matrix, uint32_t n_cols, ui
 int zkl_hip_plan_row_prefix(const uint32_t* period, uint32_t n_cols, uint64_t n_lde_rows, uint32_t blowup,
                             uint32_t num_partitions, uint32_t hash_rate, uint32_t* lead_out, uint32_t* q_out,
                             uint32_t* n_parts_out);
+/* Zero mask of the same plan (host code, no device): in the blocks a partition still absorbs the
+ * row kernel does not load columns the scan found zero.  Per partition p < *n_parts_out, bit j of
+ * even_out[p] = column 2j of the partition is zero, bit j of odd_out[p] = column 2j + 1 is zero or
+ * absent (the lone last column of an odd partition).  A partition of more than 64 pairs gets an
+ * empty mask (both words 0) and loads everything; rows of more than 9 partitions have no plan
+ * (*n_parts_out = 0).  even_out and odd_out have 16 entries. */
+int zkl_hip_plan_row_zero_mask(const uint32_t* period, uint32_t n_cols, uint32_t num_partitions, uint32_t hash_rate,
+                               uint64_t* even_out, uint64_t* odd_out, uint32_t* n_parts_out);
+/* Process-wide switch of the zero mask alone, default 1 (ZKL_ROW_ZERO_MASK=0 in the environment
+ * starts it at 0); 0 makes the prefix row kernel load every column.  For A/B runs; digests do not
+ * depend on it. */
+int zkl_hip_set_row_zero_mask(int on);
+int zkl_hip_row_zero_mask(void);
 /* zkl_hip_hash_rows with per-column row periods the caller asserts (in rows of d_matrix, natural
  * row order); split = 1: d_matrix is an LDE in the split layout (zkl_hip_lde_columns) and the
  * digests are written in natural row order.  The plan is zkl_hip_plan_row_prefix's with blowup 1,

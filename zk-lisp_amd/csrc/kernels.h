@@ -116,12 +116,22 @@ struct RowPrefixPlan {
   uint32_t np = 0;  // partitions of the row (as launch_hash_rows splits it)
   uint32_t lead[16] = {0};
   uint32_t q[16] = {0};  // meaningful where lead > 0
+  // zero mask of every partition (lead 0 included): bit j of zeven[p] = column 2j of the partition
+  // is zero (period 0), of zodd[p] = column 2j + 1 is zero or absent (the lone last column of an
+  // odd partition).  Both 0: no mask (more than ROW_MASK_PAIRS pairs, or more than 9 partitions).
+  uint64_t zeven[16] = {0};
+  uint64_t zodd[16] = {0};
   bool any() const {
     for (uint32_t p = 0; p < np; p++)
       if (lead[p]) return true;
     return false;
   }
 };
+constexpr uint32_t ROW_MASK_PAIRS = 64;  // folded pairs per partition a zero mask can describe
+// The zero mask alone has a switch of its own for A/B runs: default 1, ZKL_ROW_ZERO_MASK=0 or the
+// setter make the prefix row kernel load every column again.  The plan carries the masks either way.
+bool row_zero_mask_enabled();
+void set_row_zero_mask(bool on);
 // Pure host code.  period: per column as above, in rows of the matrix before the blowup (a
 // period P becomes blowup * P LDE rows; zero and constant columns stay so).  A partition's prefix
 // is used only when its q <= n_rows / rows_per_entry; rows of more than 9 partitions keep the dense path.

@@ -599,6 +599,19 @@ bool column_structure_enabled() {
 }
 void set_column_structure(bool on) { g_colstruct.store(on ? 1 : 0); }
 
+static std::atomic<int> g_row_zero_mask{-1};
+bool row_zero_mask_enabled() {
+  int v = g_row_zero_mask.load();
+  if (v < 0) {
+    const char* e = getenv("ZKL_ROW_ZERO_MASK");
+    v = !(e && !strcmp(e, "0"));
+    int expect = -1;
+    if (!g_row_zero_mask.compare_exchange_strong(expect, v)) v = expect;
+  }
+  return v != 0;
+}
+void set_row_zero_mask(bool on) { g_row_zero_mask.store(on ? 1 : 0); }
+
 RowPrefixPlan plan_row_prefix(const uint32_t* period, uint32_t ncols, size_t nrows, uint32_t blowup, uint32_t np,
                               uint32_t rate, size_t rows_per_entry) {
   RowPrefixPlan pl;
@@ -614,6 +627,11 @@ RowPrefixPlan plan_row_prefix(const uint32_t* period, uint32_t ncols, size_t nro
   for (uint32_t p = 0; p < np_eff; p++) {
     const uint32_t c0 = p * psize, len = std::min(psize, ncols - c0);
     const uint32_t total = (len + 1) / 2 + 1;  // sponge elements: the domain element, then the folded pairs
+    if (total - 1 <= ROW_MASK_PAIRS)
+      for (uint32_t j = 0; j < total - 1; j++) {
+        if (period[c0 + 2 * j] == 0) pl.zeven[p] |= (uint64_t)1 << j;
+        if (2 * j + 1 >= len || period[c0 + 2 * j + 1] == 0) pl.zodd[p] |= (uint64_t)1 << j;
+      }
     uint32_t lead = 0;
     uint64_t pmax = 1;
     for (uint32_t b0 = 0; b0 < total; b0 += 10) {
@@ -663,7 +681,12 @@ bool launch_hash_rows_prefix(const fe* d_mat, uint32_t ncols, size_t nrows, uint
   A.table = d_table;
   uint32_t off = 0;
   size_t items = 0;
+  const bool masked = row_zero_mask_enabled();
   for (uint32_t p = 0; p < np_eff; p++) {
+    if (masked) {
+      A.zeven[p] = pl.zeven[p];
+      A.zodd[p] = pl.zodd[p];
+    }
     if (!pl.lead[p]) continue;
     const uint32_t len = std::min(psize, ncols - p * psize), blocks = ((len + 1) / 2 + 1 + 9) / 10, q = pl.q[p];
     if (pl.lead[p] > blocks || q == 0 || (q & (q - 1)) || q > nrows)

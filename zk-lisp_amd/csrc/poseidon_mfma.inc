@@ -454,6 +454,41 @@ __device__ __forceinline__ void pm_sponge_blocks(const PmTables* tb, bool live, 
   }
 }
 
+// pm_sponge_blocks<false> of the masked row kernel: the same blocks and the same first-block
+// pruning (by nmsg alone), but skip(i) (wave-uniform) says that sponge elements i and i + 1, the two half-waves
+// of one T, absorb only zeros, and that T's fold, conversion and limb adds are left out.  A copy and
+// not a parameter of the routine above: with the parameter the dense row kernel came out with
+// its registers renamed, and its code is to stay what it was.
+template <class Loader, class Skip>
+__device__ __forceinline__ void pm_sponge_blocks_masked(const PmTables* tb, bool live, int nmsg, Loader ld,
+                                                        uint32_t x[6][5], int h, int b_from, int b_to, Skip skip) {
+  const int total = nmsg + 1;
+  for (int b0 = b_from; b0 < b_to; b0 += 10) {
+    // every load of the block is issued before the first fold waits for one: one memory latency
+    // per block instead of one per T (the registers are free here, between two permutations)
+    fe ca[5], cb[5];
+#pragma unroll
+    for (int T = 0; T < 5; T++) {
+      const int idx = b0 + 2 * T + h;
+      ca[T] = cb[T] = fe_zero();
+      if (skip(b0 + 2 * T)) continue;
+      if (live && idx >= 1 && idx < total) ld(idx - 1, ca[T], cb[T]);
+    }
+#pragma unroll
+    for (int T = 0; T < 5; T++) {
+      const int idx = b0 + 2 * T + h;
+      if (skip(b0 + 2 * T)) continue;
+      if (live && idx >= 1 && idx < total) {
+        uint32_t m[5];
+        to_mont130(fold_pair(ca[T], cb[T]), m);
+#pragma unroll
+        for (int l = 0; l < 5; l++) x[T][l] += m[l];
+      }
+    }
+    pm_permute(tb, x, (PM_PRUNE_CFG & 1) && b0 == 0 ? pm_first_const_mask(nmsg) : 0, false);
+  }
+}
+
 template <int D, bool OUT0 = true, class Loader>
 __device__ __forceinline__ fe pm_sponge(const PmTables* tb, bool live, int nmsg, Loader ld) {
   const int h = (int)((threadIdx.x >> 5) & 1);
@@ -731,6 +766,9 @@ struct PmRowPrefix {
   uint32_t lead[PM_PFX_PARTS];   // leading absorb blocks taken from the table (0: none)
   uint32_t qmask[PM_PFX_PARTS];  // Q[p] - 1
   uint32_t off[PM_PFX_PARTS];    // first table entry of partition p
+  // zero mask (hash_rows_pm_prefix_kernel): bit j of zeven[p] = column 2j of partition p is all
+  // zero, of zodd[p] = column 2j + 1 is all zero or absent; both 0 = no mask, every column loaded
+  uint64_t zeven[PM_PFX_PARTS], zodd[PM_PFX_PARTS];
 };
 constexpr int PM_PFX_ENTRY_WORDS = 60;
 
@@ -826,12 +864,18 @@ __global__ __launch_bounds__(PM_ROW_THREADS) void hash_rows_pm_prefix_kernel(con
       } else {
         pm_sponge_init<DOM_ELEMS>(x);
       }
+      // a masked column's load does not issue; where both pairs of a T are zero (scalar test of the
+      // mask: pair j is sponge element j + 1) the T is skipped whole
+      const uint64_t ze = A.zeven[p], zo = A.zodd[p], zpair = ze & zo;  // wave-uniform
       // first-block pruning applies only to a sponge that starts at block 0 (pm_sponge_blocks)
-      pm_sponge_blocks<false>(&tb, live, nmsg, [&](int j) {
-        fe a = base[(size_t)(2 * j) * nrows];
-        fe b = (2u * j + 1 < len) ? base[(size_t)(2 * j + 1) * nrows] : fe_zero();
-        return fold_pair(a, b);
-      }, x, pm_h, 10 * (int)lead, nmsg + 1);
+      pm_sponge_blocks_masked(&tb, live, nmsg, [&](int j, fe& a, fe& b) {  // a, b zero on entry
+        if (!((ze >> (j & 63)) & 1)) a = base[(size_t)(2 * j) * nrows];
+        if (!(((zo >> (j & 63)) & 1) || 2u * j + 1 >= len)) b = base[(size_t)(2 * j + 1) * nrows];
+      }, x, pm_h, 10 * (int)lead, nmsg + 1, [&](int i) {
+        const bool z0 = i < 1 || i > nmsg || ((zpair >> ((i - 1) & 63)) & 1);
+        const bool z1 = i >= nmsg || ((zpair >> (i & 63)) & 1);
+        return z0 && z1;
+      });
       d = from_mont130(x[0]);
       if (merge) {
         const fe v = pm_from_low_half(d);

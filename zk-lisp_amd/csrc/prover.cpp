@@ -2001,6 +2001,30 @@ int zkl_hip_plan_row_prefix(const uint32_t* period, uint32_t nc, uint64_t n_lde_
   });
 }
 
+int zkl_hip_plan_row_zero_mask(const uint32_t* period, uint32_t nc, uint32_t np, uint32_t rate, uint64_t* even_out,
+                               uint64_t* odd_out, uint32_t* n_parts_out) {
+  if (!period || !even_out || !odd_out || !n_parts_out || nc == 0 || np < 1 || np > 16 || rate < 1 || rate > 256)
+    return ZKL_E_INVALID;
+  return run_guarded(nullptr, [&] {
+    // the masks depend on neither the row count nor the blowup
+    const RowPrefixPlan pl = plan_row_prefix(period, nc, 1, 1, np, rate);
+    const bool planned = pl.np >= 1 && pl.np <= 9;
+    for (int p = 0; p < 16; p++) {
+      even_out[p] = planned ? pl.zeven[p] : 0;
+      odd_out[p] = planned ? pl.zodd[p] : 0;
+    }
+    *n_parts_out = planned ? pl.np : 0;
+  });
+}
+
+int zkl_hip_set_row_zero_mask(int on) {
+  if (on < 0 || on > 1) return ZKL_E_INVALID;
+  set_row_zero_mask(on != 0);
+  return 0;
+}
+
+int zkl_hip_row_zero_mask(void) { return row_zero_mask_enabled() ? 1 : 0; }
+
 int zkl_hip_hash_rows_periodic(zkl_ctx* c, const void* d_m, uint32_t nc, uint32_t nr, uint32_t np, uint32_t rate,
                                const uint32_t* row_period, int split, void* d_out, uint32_t* resumed_out) {
   if (resumed_out) *resumed_out = 0;

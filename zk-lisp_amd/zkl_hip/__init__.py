@@ -214,6 +214,10 @@ def load_library():
     lib.zkl_hip_scan_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(C.c_uint32)]
     lib.zkl_hip_plan_row_prefix.argtypes = [P(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                             P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
+    lib.zkl_hip_plan_row_zero_mask.argtypes = [P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint64),
+                                               P(C.c_uint64), P(C.c_uint32)]
+    lib.zkl_hip_set_row_zero_mask.argtypes = [C.c_int]
+    lib.zkl_hip_row_zero_mask.argtypes = []
     lib.zkl_hip_hash_rows_periodic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                P(C.c_uint32), C.c_int, C.c_void_p, P(C.c_uint32)]
     lib.zkl_hip_lde_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32),
@@ -572,6 +576,40 @@ def plan_row_prefix(periods, n_lde_rows: int, blowup: int, num_partitions: int, 
         raise ZklError(rc, "zkl_hip_plan_row_prefix: invalid arguments")
     k = np_.value
     return tuple(lead[:k]), tuple(q[p] if lead[p] else None for p in range(k))
+
+
+def plan_row_zero_mask(periods, num_partitions: int, hash_rate: int = 16):
+    """Host planning of the row hash's zero mask: per partition of the row, (even, odd) with bit j of
+    even = column 2j of the partition is zero and bit j of odd = column 2j + 1 is zero or absent;
+    (0, 0) for a partition of more than 64 pairs.  None for rows of more than 9 partitions."""
+    lib = load_library()
+    per = (C.c_uint32 * len(periods))(*[int(x) for x in periods])
+    even, odd, np_ = (C.c_uint64 * 16)(), (C.c_uint64 * 16)(), C.c_uint32(0)
+    rc = lib.zkl_hip_plan_row_zero_mask(per, len(periods), num_partitions, hash_rate, even, odd, C.byref(np_))
+    if rc != 0:
+        raise ZklError(rc, "zkl_hip_plan_row_zero_mask: invalid arguments")
+    if np_.value == 0:
+        return None
+    return tuple((even[p], odd[p]) for p in range(np_.value))
+
+
+class row_zero_mask:
+    """Context manager: the process-wide switch of the row hash's zero mask
+    (zkl_hip_set_row_zero_mask) for the duration of the block."""
+
+    def __init__(self, on: bool):
+        self.on = 1 if on else 0
+
+    def __enter__(self):
+        lib = load_library()
+        self.prev = lib.zkl_hip_row_zero_mask()
+        if lib.zkl_hip_set_row_zero_mask(self.on) != 0:
+            raise ZklError(-1, "zkl_hip_set_row_zero_mask failed")
+        return self
+
+    def __exit__(self, *exc):
+        load_library().zkl_hip_set_row_zero_mask(self.prev)
+        return False
 
 
 def device_count() -> int:
