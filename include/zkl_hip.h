@@ -525,6 +525,35 @@ int zkl_build_segment_trace(const zkl_program* prog, uint32_t r_start, uint32_t 
                             zkl_air_public_inputs* pi_out, uint32_t* width_out, uint8_t state_in[32],
                             uint8_t state_out[32]);
 void zkl_program_free(zkl_program* prog);
+/* The same public inputs, width and state hashes with no trace: what the caller of a device build
+ * needs on the host.  Everything comes from the ops and zkl_program_new's pre-pass (which also
+ * logs ROM lane 0 and the one or two register values each level writes, 48 B per level), so a
+ * call runs one t=3 permutation (rom_s_out), no inversion, and reads or writes no trace cell.
+ * Same window rules as zkl_build_segment_trace; pi_out NULL: only *width_out.  Calls on one
+ * program may run concurrently. */
+int zkl_segment_inputs(const zkl_program* prog, uint32_t r_start, uint32_t r_end, zkl_air_public_inputs* pi_out,
+                       uint32_t* width_out, uint8_t state_in[32], uint8_t state_out[32]);
+/* zkl_build_segment_trace on the device: replaces the input side of prove_segment
+ * (prove.rs:1057-1134, build_segment_trace_with_state_without_full mod.rs:316-365) with a fill of
+ * caller memory on ctx's device (e.g. from zkl_hip_device_alloc), so a segment costs an upload of
+ * a few hundred bytes per level instead of width x rows x 16.  The host stages one record per
+ * level (op fields, registers before and after, sponge selectors, Merkle accumulator, load value,
+ * ROM lane 0), the slices of the sorted RAM table and its running sums the rows show, and the
+ * program's constants, through a pinned buffer the context owns; the kernel recomputes the
+ * Poseidon and ROM rounds, the inversions and the bit columns and writes every cell of the
+ * column-major width x (r_end - r_start) trace: bit for bit zkl_build_segment_trace's, with the
+ * same pi, width and state hashes.  The fill runs on ctx's stream, so a following
+ * zkl_hip_prove_segment_device* or zkl_hip_check_trace_device on ctx is ordered after it; other
+ * readers call zkl_hip_synchronize first.  cap_bytes < width x rows x 16: ZKL_E_INVALID, nothing
+ * written.  d_trace_out NULL: only *width_out.  Nothing is kept per program: prog may be freed
+ * after the call.  Calls on one program from several contexts may run concurrently. */
+int zkl_hip_build_segment_trace_device(zkl_ctx* ctx, const zkl_program* prog, uint32_t r_start, uint32_t r_end,
+                                       void* d_trace_out, size_t cap_bytes, zkl_air_public_inputs* pi_out,
+                                       uint32_t* width_out, uint8_t state_in[32], uint8_t state_out[32]);
+/* Device time (ms) of the last zkl_hip_build_segment_trace_device on ctx, upload and fill, by HIP
+ * events on its stream; waits for the fill.  Recorded only for builds made with
+ * zkl_hip_set_kernel_timing(ctx, 2) (ZKL_E_INVALID otherwise). */
+int zkl_hip_build_device_ms(zkl_ctx* ctx, double* ms_out);
 
 /* n segment proofs verified as zkl_verify_segment verifies each (same checks, same verdict, same
  * message), with the Poseidon hashing of the openings and the composition-coefficient draws on

@@ -396,6 +396,22 @@ class Program {
     Segment s = build_segment_into(r_start, r_end, t.data());
     return {std::move(t), s};
   }
+  // the same segment info with no trace (zkl_segment_inputs): what a device build's caller needs
+  Segment segment_inputs(uint32_t r_start, uint32_t r_end) const {
+    Segment s;
+    detail::check(zkl_segment_inputs(p_, r_start, r_end, &s.pi, &s.width, s.state_in.data(), s.state_out.data()));
+    return s;
+  }
+  // build_segment_into with the trace written on the device (zkl_hip_build_segment_trace_device):
+  // d_out is cap_bytes of memory on dev's device; the fill is ordered before the next prove or
+  // check on dev
+  Segment build_segment_device(Device& dev, uint32_t r_start, uint32_t r_end, void* d_out, size_t cap_bytes) const {
+    Segment s;
+    detail::check(zkl_hip_build_segment_trace_device(dev.ctx(), p_, r_start, r_end, d_out, cap_bytes, &s.pi, &s.width,
+                                                     s.state_in.data(), s.state_out.data()),
+                  dev.ctx());
+    return s;
+  }
 
  private:
   zkl_program* p_ = nullptr;

@@ -29,6 +29,7 @@
 #include "lde_plan.h"
 #include "host_proof.h"
 #include "preflight.h"
+#include "tracegen_dev.h"
 #include "proof_view.h"
 
 using namespace zkl;
@@ -185,6 +186,11 @@ struct zkl_ctx {
   DBuf pf_rowper, pf_col, pf_step, pf_val, pf_min;
   HBuf h_pf;
   zkl_trace_report report{};
+  // device trace builder: the staged segment description, pinned and on the device
+  HBuf h_tg;
+  DBuf tg;
+  hipEvent_t tg_ev = nullptr, tg_t0 = nullptr, tg_t1 = nullptr;  // upload done; timing pair (kernel timing 2)
+  bool tg_timed = false;
 };
 
 static const char* kFamilyNames =
@@ -1667,6 +1673,11 @@ void zkl_hip_destroy(zkl_ctx* c) {
     (void)hipEventDestroy(c->aux_ev);
     (void)hipEventDestroy(c->hev);
   }
+  if (c->tg_ev) {
+    (void)hipEventDestroy(c->tg_ev);
+    (void)hipEventDestroy(c->tg_t0);
+    (void)hipEventDestroy(c->tg_t1);
+  }
   delete c;
 }
 
@@ -1779,6 +1790,68 @@ int zkl_hip_check_trace(zkl_ctx* c, const zkl_f128* trace, uint32_t width, uint3
   });
   if (!rc) *out = c->report;
   return rc;
+}
+
+// The host stages the segment outside the context's lock (a proof may be running on it), then
+// copies the blob into the pinned buffer, uploads it and launches the fill on the proof stream.
+// The call returns once the upload has left the pinned buffer; the fill itself is only ordered.
+int zkl_hip_build_segment_trace_device(zkl_ctx* c, const zkl_program* prog, uint32_t r_start, uint32_t r_end,
+                                       void* d_trace_out, size_t cap_bytes, zkl_air_public_inputs* pi_out,
+                                       uint32_t* width_out, uint8_t state_in[32], uint8_t state_out[32]) {
+  if (!c || !prog) return ZKL_E_INVALID;
+  TraceGenStage st;
+  if (int rc = tracegen_stage_size(prog, r_start, r_end, &st)) {
+    set_err(c, "build_segment_trace_device: rows must be whole levels of the program, a power of two long");
+    return rc;
+  }
+  if (width_out) *width_out = st.width;
+  if (!d_trace_out) return ZKL_OK;
+  if (!pi_out) return ZKL_E_INVALID;
+  if (cap_bytes < (size_t)st.width * st.rows * sizeof(fe)) {
+    set_err(c, "build_segment_trace_device: the destination is smaller than width x rows x 16 bytes");
+    return ZKL_E_INVALID;
+  }
+  thread_local std::vector<fe> blob;  // kept per thread: a builder thread stages segment after segment
+  return run_guarded(c, [&] {
+    blob.resize((st.bytes + sizeof(fe) - 1) / sizeof(fe));
+    if (int rc = tracegen_stage(prog, r_start, r_end, &st, blob.data(), pi_out, state_in, state_out))
+      throw std::runtime_error("build_segment_trace_device: staging failed (" + std::to_string(rc) + ")");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHECK(hipSetDevice(c->device));
+    c->zero_stage.forget();  // this call writes caller memory
+    if (!c->tg_ev) {
+      HIPCHECK(hipEventCreateWithFlags(&c->tg_ev, hipEventDisableTiming));
+      HIPCHECK(hipEventCreate(&c->tg_t0));
+      HIPCHECK(hipEventCreate(&c->tg_t1));
+    }
+    c->tg_timed = c->ktiming == 2;
+    if (c->tg_timed) HIPCHECK(hipEventRecord(c->tg_t0, c->stream));
+    c->h_tg.ensure(st.bytes);
+    c->tg.ensure(st.bytes);
+    memcpy(c->h_tg.p, blob.data(), st.bytes);
+    HIPCHECK(hipMemcpyAsync(c->tg.p, c->h_tg.p, st.bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipEventRecord(c->tg_ev, c->stream));
+    launch_trace_fill(c->tg.p, st.rows / 32, st.width, (fe*)d_trace_out, c->stream);
+    HIPCHECK(hipGetLastError());
+    if (c->tg_timed) HIPCHECK(hipEventRecord(c->tg_t1, c->stream));
+    HIPCHECK(hipEventSynchronize(c->tg_ev));
+  });
+}
+
+int zkl_hip_build_device_ms(zkl_ctx* c, double* ms_out) {
+  if (!c || !ms_out) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->tg_timed) {
+    set_err(c, "no timed device build on this context (zkl_hip_set_kernel_timing(ctx, 2) before the build)");
+    return ZKL_E_INVALID;
+  }
+  return run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    HIPCHECK(hipEventSynchronize(c->tg_t1));
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, c->tg_t0, c->tg_t1));
+    *ms_out = ms;
+  });
 }
 
 int zkl_hip_set_preflight(zkl_ctx* c, int on) {

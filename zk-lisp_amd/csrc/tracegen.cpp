@@ -14,6 +14,11 @@
 // prove.rs:1103-1113) without the full trace in memory -- examples/fib-2pow16.zlisp has 2^24
 // rows (~55 GB at 204 columns) in 256 segments of 2^16.
 //
+// The pre-pass also logs ROM lane 0 and the register writes of every level, so a window's
+// per-level state follows from a checkpoint by replaying writes: zkl_segment_inputs derives a
+// segment's public inputs and state hashes with no trace, and tracegen_stage writes what the
+// device builder (tracegen.hip) fills a segment from.
+//
 // Synthetic program (splitmix64 choices, immediates < 2^63, End on the last level):
 //   flags 0            Const/Add/Mov/Mul over r0..r7
 //   ZKL_SYN_SPONGE     8-level block absorb, const, absorb, squeeze, add, mov, mul, squeeze
@@ -36,6 +41,7 @@
 #include "../../include/zkl_hip.h"
 #include "air_host.h"
 #include "host_hash.h"
+#include "tracegen_dev.h"
 
 using namespace zkl;
 
@@ -149,6 +155,11 @@ struct Run {
   std::vector<fe> gp_sorted;      // gp_sorted[k]: sum of the first k sorted compressions
   std::vector<fe> last_write;     // ram_s_last_write after k sorted rows
   std::vector<fe> gp_unsorted;    // gp_unsorted[k]: sum of the first k level-order compressions
+  // per-level logs (48 B per level): what a window's per-level state is replayed from without
+  // a field multiplication (replay_level)
+  std::vector<fe> rom0_log;       // ROM lane 0 entering level l; [levels]: leaving the last
+  std::vector<fe> wr_log;         // [2 l], [2 l + 1]: the values level l writes to dst (a Merkle
+                                  // level: its accumulator) and dst2
   fe rom_final[3];
   fe merkle_root = fe_zero();
   bool has_root = false;
@@ -540,13 +551,21 @@ int prepass(Run& R) {
   R.cks.clear();
   R.events.clear();
   fe s[3] = {c.rom0, fe_zero(), fe_zero()};
+  R.rom0_log.assign(R.levels + 1, fe_zero());
+  R.wr_log.assign(2 * R.levels, fe_zero());
   for (size_t l = 0; l < R.levels; l++) {
     if (l % CK == 0) R.cks.push_back(c);
+    R.rom0_log[l] = c.rom0;
     if (int rc = vm_level(R, l, c, nullptr, &mem, &R.events)) return rc;
-    if (R.ops[l].k == K_MLAST) { R.merkle_root = c.merkle_out; R.has_root = true; }
+    const Op& o = R.ops[l];
+    const bool mk = o.k == K_MFIRST || o.k == K_MSTEP || o.k == K_MLAST;
+    R.wr_log[2 * l] = mk ? c.merkle_out : c.regs[o.dst];
+    R.wr_log[2 * l + 1] = c.regs[o.dst2];
+    if (o.k == K_MLAST) { R.merkle_root = c.merkle_out; R.has_root = true; }
     rom_level(R, l, c.rom0, nullptr, s);
     c.rom0 = s[0];
   }
+  R.rom0_log[R.levels] = s[0];
   memcpy(R.rom_final, s, sizeof s);
   // the sorted table: (addr, clk) keys, clocks unique per address (one event per level)
   R.sorted = R.events;
@@ -1069,21 +1088,42 @@ extern "C" int zkl_program_new(const zkl_op* ops, uint32_t n_ops, const uint8_t 
 
 extern "C" void zkl_program_free(zkl_program* p) { delete p; }
 
+namespace {
+// Rows [r_start, r_end) of a program as a segment: its levels, effective feature mask and layout
+struct Window {
+  size_t l0, l1, m;
+  uint64_t eff;
+  bool e_ram, e_merkle;
+  Layout LS;
+};
+int window_of(const Run& R, uint32_t r_start, uint32_t r_end, Window& w) {
+  const size_t n = R.levels * 32;
+  if (r_start >= r_end || r_end > n || r_start % 32 || r_end % 32) return ZKL_E_INVALID;
+  w.m = r_end - r_start;
+  if (w.m & (w.m - 1)) return ZKL_E_INVALID;  // a Winterfell trace length
+  size_t n_ops = R.levels;
+  while (n_ops > 0 && R.ops[n_ops - 1].k == K_PAD) n_ops--;
+  w.l0 = r_start / 32;
+  w.l1 = r_end / 32;
+  w.eff = segment_mask(program_mask(R), R.ops, n_ops, w.l0, w.l1);
+  w.e_ram = w.eff & FM_RAM;
+  w.e_merkle = w.eff & FM_MERKLE;
+  w.LS = make_layout(true, w.e_ram, (w.eff & FM_SPONGE) != 0, w.e_merkle, true);
+  return ZKL_OK;
+}
+}  // namespace
+
 extern "C" int zkl_build_segment_trace(const zkl_program* p, uint32_t r_start, uint32_t r_end, zkl_f128* trace_out,
                                        zkl_air_public_inputs* pi_out, uint32_t* width_out, uint8_t state_in[32],
                                        uint8_t state_out[32]) {
   if (!p) return ZKL_E_INVALID;
   const Run& R = p->R;
-  const size_t n = R.levels * 32;
-  if (r_start >= r_end || r_end > n || r_start % 32 || r_end % 32) return ZKL_E_INVALID;
-  const size_t m = r_end - r_start;
-  if (m & (m - 1)) return ZKL_E_INVALID;  // a Winterfell trace length
-  size_t n_ops = R.levels;
-  while (n_ops > 0 && R.ops[n_ops - 1].k == K_PAD) n_ops--;
-  const size_t l0 = r_start / 32, l1 = r_end / 32;
-  const uint64_t eff = segment_mask(program_mask(R), R.ops, n_ops, l0, l1);
-  const bool e_ram = eff & FM_RAM, e_merkle = eff & FM_MERKLE;
-  const Layout LS = make_layout(true, e_ram, (eff & FM_SPONGE) != 0, e_merkle, true);
+  Window win;
+  if (int rc = window_of(R, r_start, r_end, win)) return rc;
+  const size_t m = win.m, l0 = win.l0, l1 = win.l1;
+  const uint64_t eff = win.eff;
+  const bool e_ram = win.e_ram, e_merkle = win.e_merkle;
+  const Layout& LS = win.LS;
   if (width_out) *width_out = (uint32_t)LS.width;
   if (!trace_out) return ZKL_OK;
   if (!pi_out) return ZKL_E_INVALID;
@@ -1107,5 +1147,313 @@ extern "C" int zkl_build_segment_trace(const zkl_program* p, uint32_t r_start, u
   derive_trace_pi(TS, LS, e_ram, m / 32, pi_out);
   if (state_in) vm_state_hash(TS, LS, 0, state_in);
   if (state_out) vm_state_hash(TS, LS, m - 1, state_out);
+  return ZKL_OK;
+}
+
+// ---- segment inputs without the trace; staging for the device builder ----------------------------
+namespace {
+bool is_merkle(Kind k) { return k == K_MFIRST || k == K_MSTEP || k == K_MLAST; }
+bool is_mem(Kind k) { return k == K_LOAD || k == K_STORE; }
+// the op puts a dst0 selector on its final row: the ALU ops, loads and squeezes
+bool selects_dst0(Kind k) {
+  return k != K_ABSORB && !is_merkle(k) && k != K_STORE && k != K_END && k != K_PAD;
+}
+bool writes_dst1(Kind k) { return k == K_DIVMOD || k == K_DIV128 || k == K_MULWIDE; }
+
+// vm_level's effect on the carry, and rom_level's on ROM lane 0, from the pre-pass logs: writes
+// only, no field multiplication
+void replay_level(const Run& R, size_t l, Carry& c) {
+  const Op& o = R.ops[l];
+  const fe w0 = R.wr_log[2 * l], w1 = R.wr_log[2 * l + 1];
+  switch (o.k) {
+    case K_PAD:
+    case K_END: break;
+    case K_ABSORB:
+      for (int i = 0; i < o.nabs && c.npending < 10; i++) c.pending[c.npending++] = o.abs_regs[i];
+      break;
+    case K_SQUEEZE: c.regs[o.dst] = w0; c.npending = 0; break;
+    case K_MFIRST:
+    case K_MSTEP:
+    case K_MLAST: c.merkle_out = w0; break;
+    case K_LOAD: c.regs[o.dst] = w0; c.ev++; break;
+    case K_STORE: c.ev++; break;
+    default:
+      c.regs[o.dst] = w0;
+      if (writes_dst1(o.k)) c.regs[o.dst2] = w1;
+  }
+  c.rom0 = R.rom0_log[l + 1];
+}
+
+// the carry entering level l <= levels, replayed from the checkpoint before it
+Carry carry_at(const Run& R, size_t l) {
+  const size_t base = std::min(l, R.levels - 1) / CK * CK;
+  Carry c = R.cks[base / CK];
+  for (size_t i = base; i < l; i++) replay_level(R, i, c);
+  return c;
+}
+
+// utils::vm_state_hash_row_with_layout of a row showing these registers
+void state_hash_regs(const fe regs[8], uint8_t out[32]) {
+  uint8_t buf[15 + 8 * 16];
+  memcpy(buf, "zkl/vm/state-v1", 15);
+  for (int i = 0; i < 8; i++)
+    for (int b = 0; b < 8; b++) {
+      buf[15 + 16 * i + b] = (uint8_t)(regs[i].lo >> (8 * b));
+      buf[15 + 16 * i + 8 + b] = (uint8_t)(regs[i].hi >> (8 * b));
+    }
+  blake3_hash(buf, sizeof buf, out);
+}
+
+// The public inputs zkl_build_segment_trace reads off the trace it wrote (derive_trace_pi, the
+// boundary values), from the ops and the pre-pass alone.  One t=3 permutation (rom_s_out).
+void window_pi(const Run& R, const Window& w, zkl_air_public_inputs* pi) {
+  const size_t l0 = w.l0, l1 = w.l1;
+  core_pi(R, pi);
+  pi->segment_feature_mask = w.eff;
+  pi->pc_init = to_abi(fe{l0, 0});
+  if (R.ram) {
+    pi->ram_gp_unsorted_in = to_abi(ram_gp_unsorted_at(R, l0 * 32));
+    pi->ram_gp_unsorted_out = to_abi(ram_gp_unsorted_at(R, l1 * 32 - 1));
+    pi->ram_gp_sorted_in = to_abi(ram_gp_sorted_at(R, l0 * 32));
+    pi->ram_gp_sorted_out = to_abi(ram_gp_sorted_at(R, l1 * 32 - 1));
+  }
+  fe s_in[3] = {R.rom0_log[l0], fe_zero(), fe_zero()}, s_out[3];
+  rom_enc_op(R, R.ops[l0], s_in + 1);
+  rom_level(R, l1 - 1, R.rom0_log[l1 - 1], nullptr, s_out);
+  for (int i = 0; i < 3; i++) {
+    pi->rom_s_in[i] = to_abi(s_in[i]);
+    pi->rom_s_out[i] = to_abi(s_out[i]);
+  }
+  pi->vm_out_reg = 0;
+  pi->vm_out_row = 29;
+  for (size_t l = l1; l-- > l0;)  // vm_output_from_trace_with_layout (utils.rs:262-289)
+    if (selects_dst0(R.ops[l].k)) {
+      pi->vm_out_reg = (uint32_t)R.ops[l].dst;
+      pi->vm_out_row = (uint32_t)((l - l0) * 32 + 29);
+      break;
+    }
+  uint32_t mask = 0, ram_bits = 0;  // compute_vm_usage_mask_for_trace (prove.rs:1289-1392)
+  const size_t E = R.sorted.size();
+  for (size_t l = l0; l < l1; l++) {
+    switch (onehot_of(R.ops[l].k)) {
+      case 9: case 7: mask |= 1u << 0; break;
+      case 10: mask |= 1u << 1; break;
+      case 11: mask |= 1u << 2; break;
+      case 12: mask |= 1u << 3; break;
+      case 14: mask |= 1u << 4; break;
+      case 13: mask |= 1u << 5; break;
+      case 6: mask |= 1u << 6; break;
+      case 8: mask |= 1u << 7; break;
+      default: break;
+    }
+    if (!w.e_ram) continue;
+    for (size_t k = 3 * l; k < 3 * l + 2 && k + 1 < E; k++) {  // rows 29, 30 and the sorted row below
+      const RamEvent &e = R.sorted[k], &en = R.sorted[k + 1];
+      if (!fe_eq(e.addr, en.addr)) continue;
+      mask |= 1u << 8;
+      if (fe_less(e.clk, en.clk)) ram_bits |= (uint32_t)(en.clk.lo - e.clk.lo);
+    }
+  }
+  pi->vm_usage_mask = mask;
+  pi->ram_delta_clk_bits = ram_bits;
+}
+
+// state hashes of the window's first and last rows: a padding level shows zero registers
+void window_state_hashes(const Run& R, const Window& w, const Carry& c_in, const Carry& c_out, uint8_t state_in[32],
+                         uint8_t state_out[32]) {
+  const fe zero[8] = {};
+  if (state_in) state_hash_regs(R.ops[w.l0].k == K_PAD ? zero : c_in.regs, state_in);
+  if (state_out) state_hash_regs(R.ops[w.l1 - 1].k == K_PAD ? zero : c_out.regs, state_out);
+}
+
+// What level l's rows are a function of (tracegen_dev.h), from the carry entering it; advances c.
+int stage_level(const Run& R, size_t l, Carry& c, LevelRec& rec) {
+  const Op& o = R.ops[l];
+  memset(&rec, 0, sizeof rec);
+  rec.oh = rec.d0_map = rec.d0_fin = rec.sa = rec.sb = rec.sc = rec.d1 = -1;
+  rec.rom[0] = c.rom0;
+  rom_enc_op(R, o, rec.rom + 1);
+  if (R.ram) {
+    if (c.ev + (is_mem(o.k) ? 1 : 0) >= R.gp_unsorted.size()) return ZKL_E_INTERNAL;
+    rec.gu[0] = R.gp_unsorted[c.ev];
+    rec.gu[1] = R.gp_unsorted[c.ev + (is_mem(o.k) ? 1 : 0)];
+  }
+  if (o.k != K_PAD) {
+    const fe* regs = c.regs;
+    rec.cls = TG_VM;
+    rec.oh = (int8_t)onehot_of(o.k);
+    memcpy(rec.regs, regs, sizeof rec.regs);
+    const fe va = regs[o.a], vb = regs[o.b], vc = regs[o.c];
+    const Kind k = o.k;
+    switch (k) {
+      case K_ABSORB:
+        rec.cls |= TG_SPONGE_SEL;
+        rec.nsel = (uint8_t)o.nabs;
+        for (int i = 0; i < o.nabs; i++) rec.sel[i] = (uint8_t)o.abs_regs[i];
+        break;
+      case K_SQUEEZE:
+        rec.cls |= TG_SPONGE_SEL | TG_SQUEEZE;
+        rec.nsel = (uint8_t)c.npending;
+        for (int i = 0; i < c.npending; i++) rec.sel[i] = (uint8_t)c.pending[i];
+        rec.d0_fin = (int8_t)o.dst;
+        break;
+      case K_MFIRST:
+      case K_MSTEP:
+      case K_MLAST:
+        rec.cls |= TG_MERKLE | (k == K_MFIRST ? TG_MFIRST : 0) | (k == K_MLAST ? TG_MLAST : 0);
+        rec.macc = k == K_MFIRST ? regs[o.dst] : c.merkle_out;
+        rec.mdir = (uint8_t)o.a;
+        rec.msib = (uint8_t)o.b;
+        break;
+      case K_LOAD:
+        if (c.ev >= R.events.size()) return ZKL_E_INTERNAL;
+        rec.imm = R.events[c.ev].val;
+        rec.sa = (int8_t)o.a;
+        rec.d0_map = rec.d0_fin = (int8_t)o.dst;
+        break;
+      case K_STORE:
+        rec.sa = (int8_t)o.a;
+        rec.sb = (int8_t)o.b;
+        break;
+      case K_END: break;
+      default: {  // ALU: selectors and witnesses as vm_level writes them, inversions left to the device
+        const bool is_const = k == K_CONST || k == K_ADDR;
+        const bool has_c = k == K_SELECT || k == K_ASSERT || k == K_ASSERT_BIT || k == K_RANGE || k == K_RANGE_LO ||
+                           k == K_RANGE_HI;
+        const bool has_a = !is_const && !(has_c && k != K_SELECT);
+        const bool has_b = k == K_ADD || k == K_SUB || k == K_MUL || k == K_EQ || k == K_SELECT || k == K_DIVMOD ||
+                           k == K_DIV128 || k == K_MULWIDE;
+        rec.d0_map = rec.d0_fin = (int8_t)o.dst;
+        if (writes_dst1(k)) rec.d1 = (int8_t)o.dst2;
+        if (has_a) rec.sa = (int8_t)o.a;
+        if (has_b) rec.sb = (int8_t)o.b;
+        if (has_c) rec.sc = (int8_t)o.c;
+        const unsigned __int128 xc = as_u128(vc);
+        switch (k) {
+          case K_CONST:
+          case K_ADDR: rec.imm = fe{o.imm, 0}; break;
+          case K_EQ: rec.inv_in = fe_sub(va, vb); break;
+          case K_RANGE: {
+            const int kb = std::min(o.bits, 32);
+            rec.imm = fe_one();
+            rec.gbits = (uint32_t)(xc & (kb >= 32 ? 0xFFFFFFFFull : ((1ull << kb) - 1)));
+            break;
+          }
+          case K_RANGE_LO: rec.inv_in = fe_one(); rec.gbits = (uint32_t)xc; break;
+          case K_RANGE_HI: rec.imm = rec.inv_in = fe_one(); rec.gbits = (uint32_t)(xc >> 32); break;
+          case K_DIVMOD: rec.inv_in = from_u64((uint64_t)as_u128(vb)); break;
+          case K_DIV128: rec.imm = vc; rec.inv_in = from_u64((uint64_t)as_u128(vb)); break;
+          default: break;
+        }
+      }
+    }
+  }
+  replay_level(R, l, c);
+  if (o.k != K_PAD) memcpy(rec.next, c.regs, sizeof rec.next);
+  return ZKL_OK;
+}
+
+// the sorted-table slice a window's rows read: events [ka, kb), prefix sums [ka, kb]
+void ram_slice(const Run& R, const Window& w, size_t& ka, size_t& kb) {
+  const size_t E = R.sorted.size();
+  ka = kb = 0;
+  if (!R.ram) return;
+  ka = std::min(E, w.l0 ? 3 * w.l0 - 1 : 0);  // the event the first map row may mirror
+  kb = std::min(E, 3 * w.l1 + 1);             // ... and the one the last row looks ahead to
+}
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+}  // namespace
+
+extern "C" int zkl_segment_inputs(const zkl_program* p, uint32_t r_start, uint32_t r_end,
+                                  zkl_air_public_inputs* pi_out, uint32_t* width_out, uint8_t state_in[32],
+                                  uint8_t state_out[32]) {
+  if (!p) return ZKL_E_INVALID;
+  const Run& R = p->R;
+  Window w;
+  if (int rc = window_of(R, r_start, r_end, w)) return rc;
+  if (width_out) *width_out = (uint32_t)w.LS.width;
+  if (!pi_out) return (state_in || state_out) ? ZKL_E_INVALID : ZKL_OK;
+  window_pi(R, w, pi_out);
+  window_state_hashes(R, w, carry_at(R, w.l0), carry_at(R, w.l1), state_in, state_out);
+  return ZKL_OK;
+}
+
+int zkl::tracegen_stage_size(const zkl_program* p, uint32_t r_start, uint32_t r_end, TraceGenStage* st) {
+  if (!p || !st) return ZKL_E_INVALID;
+  const Run& R = p->R;
+  Window w;
+  if (int rc = window_of(R, r_start, r_end, w)) return rc;
+  size_t ka, kb;
+  ram_slice(R, w, ka, kb);
+  st->width = (uint32_t)w.LS.width;
+  st->rows = (uint32_t)w.m;
+  st->bytes = align16(sizeof(TraceGenHeader)) + (w.l1 - w.l0) * sizeof(LevelRec) +
+              (R.ram ? (kb - ka) * sizeof(RamEventDev) + 2 * (kb - ka + 1) * sizeof(fe) : 0);
+  return ZKL_OK;
+}
+
+int zkl::tracegen_stage(const zkl_program* p, uint32_t r_start, uint32_t r_end, const TraceGenStage* st, void* blob,
+                        zkl_air_public_inputs* pi, uint8_t state_in[32], uint8_t state_out[32]) {
+  if (!p || !st || !blob || !pi) return ZKL_E_INVALID;
+  static_assert(sizeof(RamEventDev) == sizeof(RamEvent), "the sorted table is copied as it is");
+  static_assert(sizeof(LevelRec) % 16 == 0 && sizeof(TraceGenHeader) % 16 == 0, "blob arrays stay 16-byte aligned");
+  const Run& R = p->R;
+  Window w;
+  if (int rc = window_of(R, r_start, r_end, w)) return rc;
+  size_t ka, kb;
+  ram_slice(R, w, ka, kb);
+  const size_t nlev = w.l1 - w.l0;
+  uint8_t* base = (uint8_t*)blob;
+  TraceGenHeader& H = *(TraceGenHeader*)base;
+  memset(&H, 0, sizeof H);
+  H.L = w.LS;
+  H.width = (uint32_t)w.LS.width;
+  H.n_levels = (uint32_t)nlev;
+  H.level0 = (uint32_t)w.l0;
+  H.has_ram_cols = w.e_ram;
+  H.has_merkle_cols = w.e_merkle;
+  H.prog_ram = R.ram;
+  H.n_full = (uint64_t)R.levels * 32;
+  H.n_sorted = R.sorted.size();
+  H.k_base = ka;
+  H.off_recs = align16(sizeof(TraceGenHeader));
+  H.off_sorted = H.off_recs + nlev * sizeof(LevelRec);
+  H.off_gp_sorted = H.off_sorted + (kb - ka) * sizeof(RamEventDev);
+  H.off_last_write = H.off_gp_sorted + (R.ram ? (kb - ka + 1) * sizeof(fe) : 0);
+  if (H.off_last_write + (R.ram ? (kb - ka + 1) * sizeof(fe) : 0) != st->bytes) return ZKL_E_INVALID;
+  H.pi_prog = be_from_le16(R.pid);
+  H.dom[0] = R.ps.dom[0];
+  H.dom[1] = R.ps.dom[1];
+  for (int i = 0; i < 12; i++) for (int k = 0; k < 12; k++) H.mds[i][k] = R.ps.mds[i][k];
+  for (int j = 0; j < 27; j++) for (int i = 0; i < 12; i++) H.rc[j][i] = R.ps.rc[j][i];
+  memcpy(H.mds3, R.mds3, sizeof H.mds3);
+  memcpy(H.rc3, R.rc3, sizeof H.rc3);
+  if (R.ram) {
+    memcpy(base + H.off_sorted, R.sorted.data() + ka, (kb - ka) * sizeof(RamEvent));
+    memcpy(base + H.off_gp_sorted, R.gp_sorted.data() + ka, (kb - ka + 1) * sizeof(fe));
+    memcpy(base + H.off_last_write, R.last_write.data() + ka, (kb - ka + 1) * sizeof(fe));
+  }
+  LevelRec* recs = (LevelRec*)(base + H.off_recs);
+  const Carry c_in = carry_at(R, w.l0);
+  Carry c = c_in;
+  for (size_t l = w.l0; l < w.l1; l++)
+    if (int rc = stage_level(R, l, c, recs[l - w.l0])) return rc;
+  window_pi(R, w, pi);
+  window_state_hashes(R, w, c_in, c, state_in, state_out);
+  return ZKL_OK;
+}
+
+extern "C" int zkl_tracegen_host_fill(const zkl_program* p, uint32_t r_start, uint32_t r_end, zkl_f128* trace_out,
+                                      zkl_air_public_inputs* pi_out, uint32_t* width_out, uint8_t state_in[32],
+                                      uint8_t state_out[32]) {
+  TraceGenStage st;
+  if (int rc = tracegen_stage_size(p, r_start, r_end, &st)) return rc;
+  if (width_out) *width_out = st.width;
+  if (!trace_out) return ZKL_OK;
+  std::vector<fe> blob((st.bytes + sizeof(fe) - 1) / sizeof(fe));
+  if (int rc = tracegen_stage(p, r_start, r_end, &st, blob.data(), pi_out, state_in, state_out)) return rc;
+  memset(trace_out, 0xFF, sizeof(zkl_f128) * (size_t)st.width * st.rows);  // as a caller's device buffer may be
+  static_assert(sizeof(zkl_f128) == sizeof(fe), "the trace is written as field elements");
+  trace_fill_host(blob.data(), (fe*)trace_out);
   return ZKL_OK;
 }

@@ -241,6 +241,12 @@ def load_library():
     lib.zkl_build_segment_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, P(AirPublicInputs),
                                             P(C.c_uint32), C.c_void_p, C.c_void_p]
     lib.zkl_program_free.argtypes = [C.c_void_p]
+    lib.zkl_segment_inputs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, P(AirPublicInputs), P(C.c_uint32),
+                                       C.c_void_p, C.c_void_p]
+    lib.zkl_hip_build_segment_trace_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                       C.c_size_t, P(AirPublicInputs), P(C.c_uint32), C.c_void_p,
+                                                       C.c_void_p]
+    lib.zkl_hip_build_device_ms.argtypes = [C.c_void_p, P(C.c_double)]
     lib.zkl_agg_prove.argtypes = [P(C.c_char_p), P(C.c_size_t), C.c_uint32, P(AggOptions), P(P(C.c_uint8)),
                                   P(C.c_size_t), C.c_void_p]
     lib.zkl_hip_agg_prove.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_uint32, P(AggOptions),
@@ -852,6 +858,35 @@ class Context:
                                                    C.byref(opts), C.byref(out), C.byref(ln))
         return self._finish(rc, out, ln)
 
+    def build_segment_device(self, program: "Program", r_start: int, r_end: int, d_ptr: int | None, cap: int = 0):
+        """zkl_hip_build_segment_trace_device: rows [r_start, r_end) of `program` written into
+        device memory d_ptr (>= width x rows x 16 bytes, `cap` its size) on this context's stream,
+        bit for bit Program.segment's trace: (pi, width, state_in_hash, state_out_hash).
+        d_ptr None: only the width (pi and hashes None)."""
+        w = C.c_uint32()
+        if d_ptr is None:
+            rc = self.lib.zkl_hip_build_segment_trace_device(self.ptr, program.ptr, r_start, r_end, None, 0, None,
+                                                             C.byref(w), None, None)
+            if rc:
+                self._err(rc)
+            return None, w.value, None, None
+        spi = AirPublicInputs()
+        sin, sout = (C.c_uint8 * 32)(), (C.c_uint8 * 32)()
+        rc = self.lib.zkl_hip_build_segment_trace_device(self.ptr, program.ptr, r_start, r_end, C.c_void_p(d_ptr),
+                                                         cap, C.byref(spi), C.byref(w), sin, sout)
+        if rc:
+            self._err(rc)
+        return spi, w.value, bytes(sin), bytes(sout)
+
+    def build_device_ms(self) -> float:
+        """Device time (ms, upload and fill) of the last build_segment_device made with
+        set_kernel_timing(2); waits for the fill."""
+        ms = C.c_double()
+        rc = self.lib.zkl_hip_build_device_ms(self.ptr, C.byref(ms))
+        if rc:
+            self._err(rc)
+        return ms.value
+
     def prove_segment_device_into(self, d_trace_ptr: int, width: int, n_rows: int, pi, opts, buf) -> int:
         """Same, written into `buf` (a writable ctypes / bytearray buffer kept across calls):
         returns the proof length; a buffer too small raises with the size in the message, and
@@ -1229,6 +1264,17 @@ class Program:
                                               C.byref(w), sin, sout)
         if rc:
             raise ZklError(rc, "build_segment_trace: invalid segment")
+        return spi, w.value, bytes(sin), bytes(sout)
+
+    def segment_inputs(self, r_start: int, r_end: int):
+        """zkl_segment_inputs: (pi, width, state_in_hash, state_out_hash) of the segment as
+        segment_into returns them, from the ops and the pre-pass alone (no trace)."""
+        w = C.c_uint32()
+        spi = AirPublicInputs()
+        sin, sout = (C.c_uint8 * 32)(), (C.c_uint8 * 32)()
+        rc = self.lib.zkl_segment_inputs(self.ptr, r_start, r_end, C.byref(spi), C.byref(w), sin, sout)
+        if rc:
+            raise ZklError(rc, "segment_inputs: invalid segment")
         return spi, w.value, bytes(sin), bytes(sout)
 
     def segment(self, r_start: int, r_end: int):

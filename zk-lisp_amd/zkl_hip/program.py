@@ -1,12 +1,17 @@
 """`zk-lisp prove`'s segment loop on one device (prove.rs:1000-1175): every segment of a program
-built on host threads by the per-segment builder (zkl_build_segment_trace, no full trace) straight
-into a context's pinned trace buffer (zkl_hip_trace_buffer), proved through the host-trace entry
-point (zkl_hip_prove_segment: the columns DMA'd from that buffer, overlapped with their LDE) by
-`inflight` contexts -- the reference's bounded rayon pool (prove.rs:1018-1050) -- and wrapped as
-zl1 step proofs.
+built by the per-segment builder (no full trace) and proved by `inflight` contexts -- the
+reference's bounded rayon pool (prove.rs:1018-1050) -- and wrapped as zl1 step proofs.
 
-Per context the next segment is built into the second buffer slot while the current one proves,
-so host building (~0.2 s per 65,536-row segment on one thread) overlaps the GPU.
+By default a segment is built on a host thread (zkl_build_segment_trace) straight into a context's
+pinned trace buffer (zkl_hip_trace_buffer) and proved through the host-trace entry point
+(zkl_hip_prove_segment: the columns DMA'd from that buffer, overlapped with their LDE).  Per
+context the next segment is built into the second buffer slot while the current one proves, so
+host building (~0.2 s per 65,536-row segment on one thread, which is why `builders` defaults to 8)
+overlaps the GPU.
+
+With device_build=True the trace is written on the device instead
+(zkl_hip_build_segment_trace_device): the host stages a few hundred bytes per level
+and the context fills one of its two device trace buffers, proved with prove_segment_device.
 """
 from __future__ import annotations
 
@@ -29,13 +34,16 @@ class SegmentProof:
 
 def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, builders: int = 8, segments=None,
                   queries: int = 64, blowup: int = 16, grind: int = 16, contexts=None, on_proof=None,
-                  preflight: bool = False):
+                  preflight: bool = False, device_build: bool = False):
     """Proves the segments of `plan` ([(r_start, r_end)], zkl_plan_segments) whose indices are in
     `segments` (default all): returns {index: SegmentProof}.  `contexts` may pass existing
     Contexts (then `inflight` = their count and they stay open).  on_proof(SegmentProof) runs in
     the proving thread after each proof.  preflight=True checks every segment's trace on the device
     before its proof (Context.set_preflight, on the contexts created here): a trace that violates the
-    AIR raises ZklError naming the constraint and row instead of "degree too large"."""
+    AIR raises ZklError naming the constraint and row instead of "degree too large".
+    device_build=True builds every trace on the device into one of two device buffers per context
+    (no pinned trace buffers, no trace upload); with preflight the check runs on that resident
+    trace.  SegmentProof.build_ms is then the wall time of the device build call."""
     idx = list(range(len(plan))) if segments is None else list(segments)
     own = contexts is None
     ctxs = [Context(device) for _ in range(inflight)] if own else list(contexts)
@@ -47,7 +55,10 @@ def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, bu
     # trace's width bounds every segment layout): the builders then never wait on a context
     # that is proving
     cap = program.width * max(b - a for a, b in plan) * 16
-    bufs = [[c.trace_buffer(cap, slot) for slot in (0, 1)] for c in ctxs]
+    if device_build:
+        bufs = [[c.alloc(cap) for _ in (0, 1)] for c in ctxs]
+    else:
+        bufs = [[c.trace_buffer(cap, slot) for slot in (0, 1)] for c in ctxs]
     pool = ThreadPoolExecutor(max_workers=max(1, builders))
     out, errors = {}, []
     lock = threading.Lock()
@@ -57,7 +68,10 @@ def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, bu
         m = b - a
         t0 = time.perf_counter()
         buf = bufs[k][slot]
-        pi, w, sin, sout = program.segment_into(a, b, buf)
+        if device_build:
+            pi, w, sin, sout = ctxs[k].build_segment_device(program, a, b, buf, cap)
+        else:
+            pi, w, sin, sout = program.segment_into(a, b, buf)
         rec = SegmentProof(i, (a, b), w, pi, sin, sout, proof_options(w, m, queries=queries, blowup=blowup,
                                                                            grind=grind))
         rec.build_ms = (time.perf_counter() - t0) * 1e3
@@ -72,7 +86,8 @@ def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, bu
                 rec, buf = nxt.result()
                 nxt = pool.submit(build, k, (j + 1) % 2, mine[j + 1]) if j + 1 < len(mine) else None
                 t0 = time.perf_counter()
-                rec.proof = ctx.prove_segment(buf, rec.width, rec.rows[1] - rec.rows[0], rec.pi, rec.opts)
+                prove = ctx.prove_segment_device if device_build else ctx.prove_segment
+                rec.proof = prove(buf, rec.width, rec.rows[1] - rec.rows[0], rec.pi, rec.opts)
                 rec.prove_ms = (time.perf_counter() - t0) * 1e3
                 if on_proof is not None:
                     on_proof(rec)
@@ -95,6 +110,10 @@ def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, bu
             x.join()
     finally:
         pool.shutdown(wait=True)
+        if device_build:
+            for c, pair in zip(ctxs, bufs):
+                for d in pair:
+                    c.free(d)
         if own:
             for c in ctxs:
                 c.close()
