@@ -631,12 +631,37 @@ typedef struct {
 int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                   const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                   uint8_t digest_out[32]);
-/* zkl_agg_prove with the child replay's hashing on ctx's device: same arguments, same artifact
- * bytes, same digest, same rejections.  ctx NULL is zkl_agg_prove.  Rank 0 of a multi-GPU run
- * holds a context after proving its own segments and can pass it here. */
+/* zkl_agg_prove on ctx's device: the child replay's hashing and the ZlAggAir proof itself (trace
+ * LDE, commitments, constraint composition, DEEP and FRI in the proof's field, the quadratic
+ * extension included).  The transcript, the AIR pre-check, the out-of-domain frame
+ * and grinding stay on the host, so a batch that violates ZlAggAir is rejected before any launch
+ * of the prover.  Same arguments, same artifact bytes, same digest, same rejections.  ctx NULL is
+ * zkl_agg_prove.  Rank 0 of a multi-GPU run holds a context after proving its own segments and
+ * can pass it here. */
 int zkl_hip_agg_prove(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                       const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                       uint8_t digest_out[32]);
+/* Process-wide switch of the device ZlAggAir prover, default 1 (ZKL_AGG_DEVICE_PROVER=0 in the
+ * environment starts it at 0).  0: zkl_hip_agg_prove keeps the host prover while the context's
+ * device still hashes the child replays -- same bytes, for A/B runs.  The setter takes 0 or 1
+ * (otherwise ZKL_E_INVALID).  zkl_hip_agg_prove_trace is not affected: its ctx argument chooses. */
+int zkl_hip_set_agg_device_prover(int on);
+int zkl_hip_agg_device_prover(void);
+/* Stage entry point: the ZlAggAir proof (the inner proof bytes that end the ZKLRC1 artifact) of
+ * a caller's trace, without any child.  trace: 31 columns x rows, column-major, host memory,
+ * rows a power of two in [8, 2^14); pi_elements: AggAirPublicInputs::to_elements, absorbed into
+ * the transcript seed; v_units_total / children_count: the values of the two last-row
+ * assertions.  Of opts, queries (max(queries, 16), at most 255), blowup (a power of two in
+ * [2, 128]) and grind (at most 32) are the proof options, min_security_bits >= 128 selects the
+ * quadratic extension and is not otherwise enforced here, trace_mode is ignored.  check_air != 0
+ * rejects a trace that violates ZlAggAir, on the host, before anything runs; 0 proves any trace
+ * (as ZKL_AGG_TRACE_REFERENCE does): the DEEP polynomial has degree below rows whatever the
+ * trace holds, so the proof is always produced, though a verifier rejects it when the trace
+ * is invalid.  ctx NULL: the host backend; otherwise ctx's device, same bytes.  ZKL_E_INVALID
+ * names the offending argument in zkl_hip_last_error(NULL).  The proof is freed with zkl_hip_free. */
+int zkl_hip_agg_prove_trace(zkl_ctx* ctx, const zkl_f128* trace, uint32_t rows, const zkl_f128* pi_elements,
+                            uint32_t n_pi, uint64_t v_units_total, uint32_t children_count,
+                            const zkl_agg_options* opts, int check_air, uint8_t** proof_out, size_t* proof_len);
 /* Wall times (ms) of the calling thread's last zkl_agg_prove / zkl_hip_agg_prove: [0] step decode +
  * child replay on the host (parse, transcript, DEEP / FRI arithmetic, plan), [1] hashing of the
  * replay (host executor or device incl. copies), [2] build_public + aggregation trace, [3] the

@@ -532,8 +532,9 @@ struct WinterfellBackend {
     std::vector<uint8_t> bytes;  // ZKLRC1 (proof.bin)
     Digest recursion_digest;
   };
-  // dev (optional): the child replays' Poseidon hashing runs on its GPU (zkl_hip_agg_prove) -- same
-  // artifact, digest and rejections; the aggregating rank has one after proving its own segments
+  // dev (optional): the child replays' Poseidon hashing and the ZlAggAir proof run on its GPU
+  // (zkl_hip_agg_prove) -- same artifact, digest and rejections; the aggregating rank has one
+  // after proving its own segments
   static Artifact prove(const std::vector<StepProof>& steps, const ProverOptions& opts,
                         uint32_t trace_mode = ZKL_AGG_TRACE_VALID, const Device* dev = nullptr) {
     std::vector<const uint8_t*> ptrs;

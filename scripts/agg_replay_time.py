@@ -5,11 +5,15 @@ Proves N chained synthetic 2^16-row segments on the GPU at the CLI options (the 
 bench.py's multi-segment lines: program seed P, ops seed P + i, ROM lane 0 carried from segment
 to segment), encodes the zl1 steps, then runs
 
-  agg_prove(steps)            host replay   and   agg_prove(steps, ctx=ctx)   device replay
+  agg_prove(steps)            host replay, host ZlAggAir prover
+  agg_prove(steps, ctx=ctx)   device replay, device ZlAggAir prover
+  agg_prove(steps, ctx=ctx)   under agg_device_prover(0): device replay, host prover
 
-alternately, `--reps` times each, and the same for verify_segments(proofs, ctx=ctx) against a
-loop of verify_segment.  Prints the medians, the six agg_last_times() parts of both paths
-(median per part) and whether the artifacts / verdicts are equal, as one JSON object.
+alternately, `--reps` times each (the third only where the library has the switch), and the same
+for verify_segments(proofs, ctx=ctx) against a loop of verify_segment.  Prints the medians, the
+six agg_last_times() parts of every path (median per part, and every repetition) and whether the
+artifacts / verdicts are equal, as one JSON object.  --package DIR takes the zkl_hip package from
+another build (a worktree of another commit), for A/B runs of two builds by this one script.
 
 One process, one context.  Run it under a time limit of its own, e.g.
   timeout -k 10 600 python scripts/agg_replay_time.py --children 64 --out profiles/agg_replay/n64.json
@@ -22,7 +26,6 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "zk-lisp_amd"))
 
 PROGRAM_SEED = 0x5EEDC400  # tests/golden/chain_2p16.json's program
 
@@ -34,9 +37,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--verify-proofs", type=int, default=64, help="proofs in the verify_segments comparison (0: skip)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--package", default=os.path.join(ROOT, "zk-lisp_amd"),
+                    help="directory holding the zkl_hip package to measure (default: this tree's)")
     ap.add_argument("--out", help="also write the JSON here")
     args = ap.parse_args()
 
+    sys.path.insert(0, os.path.abspath(args.package))
     import zkl_hip
     n, N = 1 << args.log_n, args.children
     ctx = zkl_hip.Context(args.device)
@@ -61,21 +67,35 @@ def main():
     res = {"children": N, "log_n": args.log_n, "reps": args.reps, "setup_s": round(setup_s, 1),
            "step_bytes": sum(len(s) for s in steps), "time_names": list(zkl_hip.AGG_TIME_NAMES)}
 
-    # ---- aggregation: host and device replay alternately (one untimed call of each first)
-    want = zkl_hip.agg_prove(steps)
-    equal = zkl_hip.agg_prove(steps, ctx=ctx) == want
-    ms = {"host": [], "device": []}
-    parts = {"host": [], "device": []}
+    # ---- aggregation: the paths alternately (one untimed call of each first)
+    switch = getattr(zkl_hip, "agg_device_prover", None)
+    paths = ["host", "device"] + (["device_host_prover"] if switch else [])
+    res["package"] = os.path.relpath(os.path.abspath(args.package), ROOT)
+    res["device_prover_switch"] = bool(switch)
+
+    def run(path):
+        if path == "host":
+            return zkl_hip.agg_prove(steps)
+        if path == "device" or not switch:
+            return zkl_hip.agg_prove(steps, ctx=ctx)
+        with switch(0):
+            return zkl_hip.agg_prove(steps, ctx=ctx)
+
+    want = run("host")
+    equal = all(run(path) == want for path in paths[1:])
+    ms = {path: [] for path in paths}
+    parts = {path: [] for path in paths}
     for _ in range(args.reps):
-        for path in ("host", "device"):
-            t, got = timed(lambda: zkl_hip.agg_prove(steps, ctx=ctx if path == "device" else None))
+        for path in paths:
+            t, got = timed(lambda: run(path))
             equal = equal and got == want
             ms[path].append(t)
             parts[path].append(zkl_hip.agg_last_times())
-    for path in ("host", "device"):
+    for path in paths:
         res[f"agg_{path}_ms"] = round(med(ms[path]), 2)
         res[f"agg_{path}_ms_all"] = [round(x, 2) for x in ms[path]]
         res[f"agg_{path}_parts_ms"] = [round(med(p[k] for p in parts[path]), 2) for k in range(6)]
+        res[f"agg_{path}_parts_ms_all"] = [[round(x, 2) for x in p] for p in parts[path]]
     res["agg_artifacts_equal"] = equal
 
     # ---- verification: the batch on the device, the batch on host threads, a loop of verify_segment

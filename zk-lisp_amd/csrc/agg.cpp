@@ -12,28 +12,32 @@
 //   artifact / digest      ZKLRC1 (lib.rs:486-551), recursion_digest_from_agg_pi (prove.rs:585-616)
 //
 // Where it runs: the aggregation trace has one row per child (>= 8 rows, 64 for BASELINE
-// configs[3]), so the ZlAggAir proof is ~10^4 Poseidon permutations plus 2^16 grinding tries and
-// stays on the host (the grinding search runs on host threads).  The child replays before it are
-// ~10^4 permutations per child: their hashing goes through the hash plan of proof_view.h, on
-// host threads (zkl_agg_prove) or on a context's device (zkl_hip_agg_prove); DESIGN.md §10 has
-// the measured split.
+// configs[3]).  The ZlAggAir proof (prove_air) is a transcript and serialisation skeleton over a
+// backend that supplies the arrays (agg_backend.h): the host loops of this file (zkl_agg_prove,
+// a NULL context, or the switch zkl_hip_set_agg_device_prover(0)) or the kernels of agg.hip on
+// a context's device (zkl_hip_agg_prove).  The transcript, the AIR pre-check, the out-of-domain
+// frame and the grinding search (host threads) stay on the host either way.  The child replays
+// before it are ~10^4 permutations per child: their hashing goes through the hash plan of
+// proof_view.h, on host threads or on the context's device; DESIGN.md §10 has the measured split.
 //
-// Quadratic extension (winter-math 0.13.1, f128 `ExtensibleField<2>` [WF-recall]): elements
-// a + b*phi with phi^2 = phi - 1, mul = [a0 b0 - a1 b1, (a0 + a1)(b0 + b1) - a0 b0], Frobenius
-// (a, b) -> (a + b, -b); serialised as two 16-byte base elements.  RandomCoin::draw::<E> reads
-// the 32 digest bytes as (a, b): the PoseidonHasher digest is a value plus 16 zero bytes, so every
-// drawn challenge has b = 0.  The arithmetic below is nevertheless the full extension field.
+// Quadratic extension: agg_air.h.  RandomCoin::draw::<E> reads the 32 digest bytes as (a, b): the
+// PoseidonHasher digest is a value plus 16 zero bytes, so every drawn challenge has b = 0.  The
+// arithmetic is nevertheless the full extension field.
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <exception>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/zkl_hip.h"
+#include "agg_backend.h"
 #include "air_host.h"
 #include "host_hash.h"
 #include "host_proof.h"
@@ -45,46 +49,13 @@ void children_root(const uint8_t suite[32], const uint8_t* digests, const uint8_
 
 namespace {
 
-struct AggError : std::invalid_argument { using std::invalid_argument::invalid_argument; };
-
 // wall times of the calling thread's last aggregation proof (zkl_agg_last_times)
 thread_local double g_agg_ms[6] = {0, 0, 0, 0, 0, 0};
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// ------------------------------------------------------------------ quadratic extension
-struct fe2 {
-  fe a, b;
-};
-inline fe2 E(fe a) { return fe2{a, fe_zero()}; }
-inline fe2 add(fe2 x, fe2 y) { return {fe_add(x.a, y.a), fe_add(x.b, y.b)}; }
-inline fe2 sub(fe2 x, fe2 y) { return {fe_sub(x.a, y.a), fe_sub(x.b, y.b)}; }
-inline fe2 mul(fe2 x, fe2 y) {
-  const fe z = fe_mul(x.a, y.a);
-  return {fe_sub(z, fe_mul(x.b, y.b)), fe_sub(fe_mul(fe_add(x.a, x.b), fe_add(y.a, y.b)), z)};
-}
-inline fe2 mulb(fe2 x, fe s) { return {fe_mul(x.a, s), fe_mul(x.b, s)}; }
-inline fe2 inv(fe2 x) {  // conj / norm, norm = a^2 + a b + b^2
-  const fe nrm = fe_add(fe_add(fe_mul(x.a, x.a), fe_mul(x.a, x.b)), fe_mul(x.b, x.b));
-  if (fe_is_zero(nrm)) throw std::runtime_error("inversion of zero in the quadratic extension");
-  const fe ni = fe_inv(nrm);
-  return {fe_mul(fe_add(x.a, x.b), ni), fe_mul(fe_sub(fe_zero(), x.b), ni)};
-}
-inline bool is_zero(fe2 x) { return fe_is_zero(x.a) && fe_is_zero(x.b); }
-// base-field helpers with the same names, so the polynomial code below is generic
-inline fe add(fe x, fe y) { return fe_add(x, y); }
-inline fe sub(fe x, fe y) { return fe_sub(x, y); }
-inline fe mulb(fe x, fe s) { return fe_mul(x, s); }
-inline fe mul(fe x, fe y) { return fe_mul(x, y); }
-template <class T> T lift(fe x);
-template <> inline fe lift<fe>(fe x) { return x; }
-template <> inline fe2 lift<fe2>(fe x) { return E(x); }
-inline bool is_zero(fe x) { return fe_is_zero(x); }
-template <class T> T zero();
-template <> inline fe zero<fe>() { return fe_zero(); }
-template <> inline fe2 zero<fe2>() { return E(fe_zero()); }
-
+// ------------------------------------------------------------------ quadratic extension (agg_air.h)
 void put(Bytes& b, fe x) { b.felem(x); }
 void put(Bytes& b, fe2 x) { b.felem(x.a); b.felem(x.b); }
 void flat(std::vector<fe>& v, fe x) { v.push_back(x); }
@@ -363,13 +334,7 @@ zkl_air_public_inputs replay_pi(const StepDecoded& s) {
 }
 
 // ------------------------------------------------------------------ aggregation trace
-// AggColumns::baseline (agg/layout.rs:97-175)
-enum AggCol {
-  C_OK, C_V0_SUM, C_V1_SUM, C_VNEXT_SUM, C_FRI_V0, C_FRI_V1, C_FRI_VNEXT, C_FRI_ALPHA, C_FRI_X0, C_FRI_X1, C_FRI_Q1,
-  C_COMP_SUM, C_ALPHA_DIV_ZM_SUM, C_MAP_L0_SUM, C_FINAL_LLAST_SUM, C_R, C_ALPHA, C_BETA, C_GAMMA, C_SEG_FIRST,
-  C_TRACE_ROOT_ERR, C_CONSTRAINT_ROOT_ERR, C_V_UNITS_ACC, C_V_UNITS_CHILD, C_CHILD_COUNT_ACC, C_VM_CHAIN_ERR,
-  C_RAM_U_CHAIN_ERR, C_RAM_S_CHAIN_ERR, C_ROM_CHAIN_ERR_0, C_ROM_CHAIN_ERR_1, C_ROM_CHAIN_ERR_2, AGG_W
-};
+// AggColumns::baseline: the AggCol enum of agg_air.h
 constexpr size_t MIN_AGG_TRACE_ROWS = 8;
 
 // fold_positions_usize (agg/child.rs:1072-1100): pos mod (size / 2), deduplicated in order
@@ -557,6 +522,36 @@ std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<C
   const fe ro0 = fold_bytes32(p.rom_initial[0]), ro1 = fold_bytes32(p.rom_final[0]);
   fe v_acc = fe_zero(), cnt = fe_zero(), pvm{}, pru{}, prs{}, pro{};
   const Weights w = agg_weights(p);
+  // per-child FRI / DEEP overlay (trace.rs:187-235, sample_fri_fold_child :1436-1685): the
+  // layer-0 sample and the four sums depend on one child alone and are most of this function's
+  // time, so they run over the children on host threads, into per-child slots, before the
+  // serial loop that chains the accumulators.  A child's error is kept in its slot and the one
+  // of the lowest child rethrown, as the serial loop would have met it first.
+  struct Overlay { fe v0, v1, vn, alpha, x0, x1, q1, comp, adz, ml0, fll; };
+  std::vector<Overlay> ov(nc);
+  {
+    std::vector<std::exception_ptr> err(nc);
+    parallel_for(nc, [&](size_t i) {
+      try {
+        const SegmentView& v = ch[i].v;
+        Overlay& o = ov[i];
+        const size_t N = v.lde, y0 = v.fri_positions[0][0];
+        o.v0 = v.fri_values[0][0];
+        o.v1 = v.fri_values[0][1];
+        o.alpha = v.fri_alphas[0];
+        o.vn = fri_fold_at(o.v0, o.v1, o.alpha, y0, N, &o.x0, &o.x1);
+        o.q1 = layer_value(v, 1, y0, N / 2);
+        o.comp = deep_agg(v, w.beta_deep);
+        o.adz = fri_layer1_agg(v, w.beta_fri_layer1);
+        o.ml0 = fri_path_agg(v, w.delta_depth, 0);
+        o.fll = fri_paths_agg(v, w.delta_depth, w.beta_paths);
+      } catch (...) {
+        err[i] = std::current_exception();
+      }
+    });
+    for (size_t i = 0; i < nc; i++)
+      if (err[i]) std::rethrow_exception(err[i]);
+  }
   for (size_t i = 0; i < nc; i++) {
     const StepDecoded& s = ch[i].step;
     const fe vm_in = fold_bytes32(s.bnd[0]), vm_out = fold_bytes32(s.bnd[1]);
@@ -591,23 +586,18 @@ std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<C
     T[C_RAM_U_CHAIN_ERR][i] = ru_err;
     T[C_RAM_S_CHAIN_ERR][i] = rs_err;
     T[C_ROM_CHAIN_ERR_0][i] = ro_err;
-    // per-child FRI / DEEP overlay (trace.rs:187-235, sample_fri_fold_child :1436-1685)
-    const SegmentView& v = ch[i].v;
-    const size_t N = v.lde, y0 = v.fri_positions[0][0];
-    fe x0, x1;
-    const fe v0 = v.fri_values[0][0], v1 = v.fri_values[0][1], alpha = v.fri_alphas[0];
-    const fe vn = fri_fold_at(v0, v1, alpha, y0, N, &x0, &x1);
-    T[C_FRI_V0][i] = v0;
-    T[C_FRI_V1][i] = v1;
-    T[C_FRI_VNEXT][i] = vn;
-    T[C_FRI_ALPHA][i] = alpha;
-    T[C_FRI_X0][i] = x0;
-    T[C_FRI_X1][i] = x1;
-    T[C_FRI_Q1][i] = layer_value(v, 1, y0, N / 2);
-    T[C_COMP_SUM][i] = deep_agg(v, w.beta_deep);
-    T[C_ALPHA_DIV_ZM_SUM][i] = fri_layer1_agg(v, w.beta_fri_layer1);
-    T[C_MAP_L0_SUM][i] = fri_path_agg(v, w.delta_depth, 0);
-    T[C_FINAL_LLAST_SUM][i] = fri_paths_agg(v, w.delta_depth, w.beta_paths);
+    const Overlay& o = ov[i];
+    T[C_FRI_V0][i] = o.v0;
+    T[C_FRI_V1][i] = o.v1;
+    T[C_FRI_VNEXT][i] = o.vn;
+    T[C_FRI_ALPHA][i] = o.alpha;
+    T[C_FRI_X0][i] = o.x0;
+    T[C_FRI_X1][i] = o.x1;
+    T[C_FRI_Q1][i] = o.q1;
+    T[C_COMP_SUM][i] = o.comp;
+    T[C_ALPHA_DIV_ZM_SUM][i] = o.adz;
+    T[C_MAP_L0_SUM][i] = o.ml0;
+    T[C_FINAL_LLAST_SUM][i] = o.fll;
     v_acc = fe_add(v_acc, fe{s.v_units, 0});
     cnt = fe_add(cnt, fe_one());
     pvm = vm_out; pru = ru_out; prs = rs_out; pro = ro_out;
@@ -620,57 +610,155 @@ std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<C
 }
 
 // ------------------------------------------------------------------ ZlAggAir (agg/air.rs)
-constexpr int AGG_TC = 24;
-struct Deg { int base; bool cycle; };  // cycle: one periodic column of period trace_len
-const Deg kAggDegrees[AGG_TC] = {{1, false}, {2, true}, {1, false}, {1, false}, {1, false}, {1, false},
-                                 {1, false}, {1, false}, {1, false}, {1, false}, {1, false}, {1, true},
-                                 {1, false}, {1, false}, {1, false}, {1, false}, {1, false}, {1, false},
-                                 {1, false}, {1, false}, {1, false}, {1, false}, {1, false}, {1, false}};
-
-// evaluate_transition (agg/air.rs:113-274); T = f128 on the trace / CE domain, the proof's
-// field E at the out-of-domain point
-template <class T>
-void agg_transition(const T* c, const T* nx, T is_last, T r[AGG_TC]) {
-  const T nl = sub(lift<T>(fe_one()), is_last);
-  auto chain = [&](int col) { return mul(nl, sub(nx[col], c[col])); };
-  r[0] = c[C_OK];
-  r[1] = mul(nl, sub(nx[C_V_UNITS_ACC], add(c[C_V_UNITS_ACC], mul(c[C_V_UNITS_CHILD], c[C_SEG_FIRST]))));
-  r[2] = c[C_TRACE_ROOT_ERR];
-  r[3] = c[C_CONSTRAINT_ROOT_ERR];
-  r[4] = chain(C_R);
-  r[5] = chain(C_ALPHA);
-  r[6] = chain(C_BETA);
-  r[7] = chain(C_GAMMA);
-  r[8] = chain(C_V0_SUM);
-  r[9] = chain(C_V1_SUM);
-  r[10] = chain(C_VNEXT_SUM);
-  r[11] = mul(nl, sub(nx[C_CHILD_COUNT_ACC], add(c[C_CHILD_COUNT_ACC], c[C_SEG_FIRST])));
-  const T xd = sub(c[C_FRI_X1], c[C_FRI_X0]);
-  r[12] = sub(mul(c[C_FRI_VNEXT], xd), sub(mul(c[C_FRI_V1], sub(c[C_FRI_ALPHA], c[C_FRI_X0])),
-                                            mul(c[C_FRI_V0], sub(c[C_FRI_ALPHA], c[C_FRI_X1]))));
-  r[13] = sub(c[C_FRI_VNEXT], c[C_FRI_Q1]);
-  r[14] = c[C_COMP_SUM];
-  r[15] = c[C_ALPHA_DIV_ZM_SUM];
-  r[16] = c[C_MAP_L0_SUM];
-  r[17] = c[C_FINAL_LLAST_SUM];
-  r[18] = c[C_VM_CHAIN_ERR];
-  r[19] = c[C_RAM_U_CHAIN_ERR];
-  r[20] = c[C_RAM_S_CHAIN_ERR];
-  r[21] = c[C_ROM_CHAIN_ERR_0];
-  r[22] = c[C_ROM_CHAIN_ERR_1];
-  r[23] = c[C_ROM_CHAIN_ERR_2];
-}
+// (AGG_TC, kAggDegrees and agg_transition<T>: agg_air.h, shared with the device prover)
 
 struct AggOpts {
   uint32_t queries, blowup, grind, field_ext;
   bool check_air = true;  // reject a trace that violates ZlAggAir (off in ZKL_AGG_TRACE_REFERENCE mode)
 };
 
-// winterfell 0.13.1 Prover::prove for ZlAggAir over E = QuadExtension<f128> (or E = f128 when
-// the security target is below 128 bits: FieldExtension::None, prove.rs:647-651)
+// The host backend of prove_air (agg_backend.h): serial loops over the host field arithmetic
+// and the host Poseidon.
 template <class T>
-std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const std::vector<fe>& pi_el, const AggPi& pi,
-                               const AggOpts& ao) {
+struct AggHostBackend final : AggBackend<T> {
+  using AggBackend<T>::sh;
+  static void put_flat(std::vector<fe>& v, const T& x) { flat(v, x); }
+  static constexpr fe off{3, 0};
+
+  fe commit_trace(const std::vector<std::vector<fe>>& trace) override {
+    const Hasher& H = hasher();
+    const size_t W = sh.W, N = sh.N;
+    this->tpoly.resize(W);
+    this->lde.resize(W);
+    for (size_t c = 0; c < W; c++) {
+      this->tpoly[c] = interpolate(trace[c], fe_one());
+      this->lde[c] = evaluate(this->tpoly[c], N, off);
+    }
+    // one partition (below 2^14 rows): partition_size == width and a row digest is hash_elements(row)
+    std::vector<fe> leaves(N), row(W);
+    for (size_t i = 0; i < N; i++) {
+      for (size_t c = 0; c < W; c++) row[c] = this->lde[c][i];
+      leaves[i] = H.hash_elements(row.data(), W);
+    }
+    this->ttree = merkle(leaves);
+    return this->ttree[1];
+  }
+
+  void compose(const std::vector<T>& alpha, const std::vector<T>& beta) override {
+    const size_t W = sh.W, n = sh.n, N = sh.N, B = sh.B, ce = sh.ce;
+    const auto& lde = this->lde;
+    // get_assertions (agg/air.rs:276-304) sorted by (step, column)
+    struct As { size_t col, step; fe v; };
+    const size_t last = n - 1;
+    const std::vector<As> asr = {{C_OK, 0, fe_zero()},
+                                 {C_V_UNITS_ACC, 0, fe_zero()},
+                                 {C_CHILD_COUNT_ACC, 0, fe_zero()},
+                                 {C_V_UNITS_ACC, last, sh.v_units_total},
+                                 {C_CHILD_COUNT_ACC, last, sh.children_count}};
+    std::vector<T> cev(ce);
+    const fe wce = root_of_unity((unsigned)ilog2(ce)), g = sh.g, gl = sh.gl;
+    fe x = off;
+    const size_t step = N / ce;
+    std::vector<fe> cur(W), nxt(W);
+    fe tc[AGG_TC];
+    for (size_t i = 0; i < ce; i++, x = fe_mul(x, wce)) {
+      for (size_t c = 0; c < W; c++) {
+        cur[c] = lde[c][i * step];
+        nxt[c] = lde[c][(i * step + B) % N];
+      }
+      const fe xn = fe_pow64(x, n), xg = fe_sub(x, gl);
+      const fe p_last = fe_mul(fe_mul(gl, fe_sub(xn, fe_one())), fe_inv(fe_mul(fe{n, 0}, xg)));
+      agg_transition<fe>(cur.data(), nxt.data(), p_last, tc);
+      T t = zero<T>();
+      for (int k = 0; k < AGG_TC; k++) t = add(t, mulb(alpha[k], tc[k]));
+      t = mulb(t, fe_mul(xg, fe_inv(fe_sub(xn, fe_one()))));
+      for (size_t a = 0; a < asr.size(); a++)
+        t = add(t, mulb(beta[a], fe_mul(fe_sub(cur[asr[a].col], asr[a].v), fe_inv(fe_sub(x, fe_pow64(g, asr[a].step))))));
+      cev[i] = t;
+    }
+    this->cco = interpolate(cev, off);
+  }
+
+  fe commit_composition() override {
+    const Hasher& H = hasher();
+    const size_t n = sh.n, N = sh.N, Cc = sh.Cc;
+    this->clde.resize(Cc);
+    for (size_t j = 0; j < Cc; j++) {
+      const std::vector<T> hp(this->cco.begin() + (long)(j * n), this->cco.begin() + (long)((j + 1) * n));
+      this->clde[j] = evaluate(hp, N, off);
+    }
+    std::vector<fe> cleaves(N), row;
+    for (size_t i = 0; i < N; i++) {
+      row.clear();
+      for (size_t j = 0; j < Cc; j++) put_flat(row, this->clde[j][i]);
+      cleaves[i] = H.hash_elements(row.data(), row.size());  // one partition: the whole row
+    }
+    this->ctree = merkle(cleaves);
+    return this->ctree[1];
+  }
+
+  void deep(T z, T zg, const std::vector<T>& frame, const std::vector<T>& gam) override {
+    const size_t W = sh.W, N = sh.N, Cc = sh.Cc;
+    const T *tz = frame.data(), *tzg = tz + W, *hz = tzg + W, *hzg = hz + Cc;
+    this->ev.resize(N);
+    const fe wN = root_of_unity((unsigned)ilog2(N));
+    fe x = off;
+    for (size_t i = 0; i < N; i++, x = fe_mul(x, wN)) {
+      const T iz = inv(sub(lift<T>(x), z)), izg = inv(sub(lift<T>(x), zg));
+      T y = zero<T>();
+      for (size_t c = 0; c < W; c++) {
+        const T t = lift<T>(this->lde[c][i]);
+        y = add(y, mul(gam[c], add(mul(sub(t, tz[c]), iz), mul(sub(t, tzg[c]), izg))));
+      }
+      for (size_t j = 0; j < Cc; j++) {
+        const T hv = this->clde[j][i];
+        y = add(y, mul(gam[W + j], add(mul(sub(hv, hz[j]), iz), mul(sub(hv, hzg[j]), izg))));
+      }
+      this->ev[i] = y;
+    }
+  }
+
+  fe fri_commit() override {
+    const Hasher& H = hasher();
+    const auto& ev = this->ev;
+    const size_t h = ev.size() / 2;
+    std::vector<fe> lf(h), row;
+    for (size_t i = 0; i < h; i++) {
+      row.clear();
+      put_flat(row, ev[i]);
+      put_flat(row, ev[i + h]);
+      lf[i] = H.hash_elements(row.data(), row.size());
+    }
+    this->ftrees.push_back(merkle(lf));
+    return this->ftrees.back()[1];
+  }
+
+  void fri_fold(T a) override {
+    auto& ev = this->ev;
+    const size_t Nd = ev.size(), h = Nd / 2;
+    const fe wd = root_of_unity((unsigned)ilog2(Nd));
+    std::vector<T> nx(h);
+    fe xe = off;
+    for (size_t i = 0; i < h; i++, xe = fe_mul(xe, wd)) {
+      const fe x0 = xe, x1 = fe_sub(fe_zero(), xe);
+      // (v1 (a - x0) - v0 (a - x1)) / (x1 - x0)
+      const T num = sub(mul(ev[i + h], sub(a, lift<T>(x0))), mul(ev[i], sub(a, lift<T>(x1))));
+      nx[i] = mulb(num, fe_inv(fe_sub(x1, x0)));
+    }
+    this->layers.push_back(std::move(ev));
+    ev = std::move(nx);
+  }
+
+  void finish() override {}
+};
+
+// winterfell 0.13.1 Prover::prove for ZlAggAir over E = QuadExtension<f128> (or E = f128 when
+// the security target is below 128 bits: FieldExtension::None, prove.rs:647-651).  This is the
+// transcript and serialisation skeleton; the arrays come from a backend (agg_backend.h): the
+// host loops above (ctx == nullptr) or the kernels of agg.hip on ctx's device.
+template <class T>
+std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const std::vector<fe>& pi_el,
+                               uint64_t v_units_total, uint32_t children_count, const AggOpts& ao, zkl_ctx* ctx) {
   const Hasher& H = hasher();
   const size_t W = trace.size(), n = trace[0].size();
   const int logn = ilog2(n);
@@ -726,89 +814,40 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
     }
     const size_t last = n - 1;
     const bool ok = fe_is_zero(trace[C_OK][0]) && fe_is_zero(trace[C_V_UNITS_ACC][0]) &&
-                    fe_is_zero(trace[C_CHILD_COUNT_ACC][0]) && fe_eq(trace[C_V_UNITS_ACC][last], fe{pi.v_units_total, 0}) &&
-                    fe_eq(trace[C_CHILD_COUNT_ACC][last], fe{pi.children_count, 0});
+                    fe_is_zero(trace[C_CHILD_COUNT_ACC][0]) && fe_eq(trace[C_V_UNITS_ACC][last], fe{v_units_total, 0}) &&
+                    fe_eq(trace[C_CHILD_COUNT_ACC][last], fe{children_count, 0});
     if (!ok) throw AggError("aggregation trace does not satisfy ZlAggAir: an assertion fails");
   }
+  // select_partitions_for_trace gives one partition below 2^14 rows (a batch of <= 2^13
+  // children); both backends hash a row whole
+  if (o.num_partitions != 1) throw AggError("aggregation traces of 2^14 rows or more are not supported");
+
+  // the arrays: host loops, or the context's device (nothing above launched anything)
+  std::unique_ptr<AggBackend<T>> be_p;
+  if (ctx) be_p = make_agg_device_backend<T>(ctx);
+  else be_p.reset(new AggHostBackend<T>());
+  AggBackend<T>& be = *be_p;
+  be.sh = AggShape{W, n, B, N, ce, Cc, g, gl, fe{v_units_total, 0}, fe{children_count, 0}};
 
   // 1. trace LDE + commitment (rows hashed whole: one partition)
-  std::vector<std::vector<fe>> tpoly(W), lde(W);
-  for (size_t c = 0; c < W; c++) {
-    tpoly[c] = interpolate(trace[c], fe_one());
-    lde[c] = evaluate(tpoly[c], N, off);
-  }
-  // select_partitions_for_trace gives one partition below 2^14 rows (a batch of <= 2^13
-  // children), so partition_size == width and a row digest is hash_elements(row)
-  if (o.num_partitions != 1) throw AggError("aggregation traces of 2^14 rows or more are not supported");
-  std::vector<fe> leaves(N);
-  {
-    std::vector<fe> row(W);
-    for (size_t i = 0; i < N; i++) {
-      for (size_t c = 0; c < W; c++) row[c] = lde[c][i];
-      leaves[i] = H.hash_elements(row.data(), W);
-    }
-  }
-  const std::vector<fe> ttree = merkle(leaves);
-  coin.reseed(ttree[1]);
+  const fe troot = be.commit_trace(trace);
+  coin.reseed(troot);
 
   // 2. constraint composition coefficients, evaluation over the CE coset
-  const int na = 5;
-  std::vector<T> alpha(AGG_TC), beta(na);
+  std::vector<T> alpha(AGG_TC), beta(AGG_NA);
   for (auto& a : alpha) a = draw(coin);
   for (auto& b : beta) b = draw(coin);
-  // get_assertions (agg/air.rs:276-304) sorted by (step, column)
-  struct As { size_t col, step; fe v; };
-  const size_t last = n - 1;
-  std::vector<As> asr = {{C_OK, 0, fe_zero()},
-                         {C_V_UNITS_ACC, 0, fe_zero()},
-                         {C_CHILD_COUNT_ACC, 0, fe_zero()},
-                         {C_V_UNITS_ACC, last, fe{pi.v_units_total, 0}},
-                         {C_CHILD_COUNT_ACC, last, fe{pi.children_count, 0}}};
-  std::vector<T> cev(ce);
-  {
-    const fe wce = root_of_unity((unsigned)ilog2(ce));
-    fe x = off;
-    const size_t step = N / ce;
-    std::vector<fe> cur(W), nxt(W);
-    fe tc[AGG_TC];
-    for (size_t i = 0; i < ce; i++, x = fe_mul(x, wce)) {
-      for (size_t c = 0; c < W; c++) {
-        cur[c] = lde[c][i * step];
-        nxt[c] = lde[c][(i * step + B) % N];
-      }
-      const fe xn = fe_pow64(x, n), xg = fe_sub(x, gl);
-      const fe p_last = fe_mul(fe_mul(gl, fe_sub(xn, fe_one())), fe_inv(fe_mul(fe{n, 0}, xg)));
-      agg_transition<fe>(cur.data(), nxt.data(), p_last, tc);
-      T t = zero<T>();
-      for (int k = 0; k < AGG_TC; k++) t = add(t, mulb(alpha[k], tc[k]));
-      t = mulb(t, fe_mul(xg, fe_inv(fe_sub(xn, fe_one()))));
-      for (size_t a = 0; a < asr.size(); a++)
-        t = add(t, mulb(beta[a], fe_mul(fe_sub(cur[asr[a].col], asr[a].v), fe_inv(fe_sub(x, fe_pow64(g, asr[a].step))))));
-      cev[i] = t;
-    }
-  }
-  // 3. composition polynomial: coset interpolation, degree check, column split, LDE, commitment
-  std::vector<T> cco = interpolate(cev, off);
+  be.compose(alpha, beta);
+  // 3. composition polynomial: degree check, column split, LDE, commitment
+  const std::vector<T>& cco = be.cco;
   for (size_t k = Cc * n; k < ce; k++)
     if (!is_zero(cco[k])) throw AggError("aggregation trace does not satisfy ZlAggAir (composition degree too large)");
-  std::vector<std::vector<T>> hpoly(Cc), clde(Cc);
-  for (size_t j = 0; j < Cc; j++) {
-    hpoly[j].assign(cco.begin() + (long)(j * n), cco.begin() + (long)((j + 1) * n));
-    clde[j] = evaluate(hpoly[j], N, off);
-  }
-  std::vector<fe> cleaves(N);
-  {
-    std::vector<fe> row;
-    for (size_t i = 0; i < N; i++) {
-      row.clear();
-      for (size_t j = 0; j < Cc; j++) put_flat(row, clde[j][i]);
-      cleaves[i] = H.hash_elements(row.data(), row.size());  // one partition: the whole row
-    }
-  }
-  const std::vector<fe> ctree = merkle(cleaves);
-  coin.reseed(ctree[1]);
+  const fe croot = be.commit_composition();
+  coin.reseed(croot);
 
-  // 4. out-of-domain frame
+  // 4. out-of-domain frame: Horner on the host over the coefficients (31 + Cc polynomials of
+  // n coefficients at two points; the device backend copies them back)
+  const std::vector<std::vector<fe>>& tpoly = be.tpoly;
   const T z = draw(coin);
   fe2 z2, zg2;
   if constexpr (sizeof(T) == sizeof(fe2)) z2 = z; else z2 = E(z);
@@ -818,7 +857,7 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   for (size_t j = 0; j < Cc; j++) {
     std::vector<fe2> hp(n);
     for (size_t k = 0; k < n; k++) {
-      if constexpr (sizeof(T) == sizeof(fe2)) hp[k] = hpoly[j][k]; else hp[k] = E(hpoly[j][k]);
+      if constexpr (sizeof(T) == sizeof(fe2)) hp[k] = cco[j * n + k]; else hp[k] = E(cco[j * n + k]);
     }
     hz[j] = eval_at(hp, z2);
     hzg[j] = eval_at(hp, zg2);
@@ -838,60 +877,29 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   // 5. DEEP composition over the LDE domain
   std::vector<T> gam(W + Cc);
   for (auto& c : gam) c = draw(coin);
-  std::vector<T> ev(N);
   {
-    const fe wN = root_of_unity((unsigned)ilog2(N));
-    fe x = off;
-    for (size_t i = 0; i < N; i++, x = fe_mul(x, wN)) {
-      const fe2 iz = inv(sub(E(x), z2)), izg = inv(sub(E(x), zg2));
-      fe2 y = E(fe_zero());
-      for (size_t c = 0; c < W; c++) {
-        const fe2 t = E(lde[c][i]);
-        const fe2 term = add(mul(sub(t, tz[c]), iz), mul(sub(t, tzg[c]), izg));
-        fe2 gc;
-        if constexpr (sizeof(T) == sizeof(fe2)) gc = gam[c]; else gc = E(gam[c]);
-        y = add(y, mul(gc, term));
-      }
-      for (size_t j = 0; j < Cc; j++) {
-        fe2 hv, gc;
-        if constexpr (sizeof(T) == sizeof(fe2)) { hv = clde[j][i]; gc = gam[W + j]; }
-        else { hv = E(clde[j][i]); gc = E(gam[W + j]); }
-        const fe2 term = add(mul(sub(hv, hz[j]), iz), mul(sub(hv, hzg[j]), izg));
-        y = add(y, mul(gc, term));
-      }
-      ev[i] = as_T(y);
-    }
+    std::vector<T> frame;  // t(z) | t(zg) | H(z) | H(zg)
+    for (auto& v : tz) frame.push_back(as_T(v));
+    for (auto& v : tzg) frame.push_back(as_T(v));
+    for (auto& v : hz) frame.push_back(as_T(v));
+    for (auto& v : hzg) frame.push_back(as_T(v));
+    be.deep(as_T(z2), as_T(zg2), frame, gam);
   }
   // 6. FRI (folding 2, constant domain offset, remainder degree 1)
   const size_t rem_max = (size_t)(o.fri_remainder_max_degree + 1) * B;
-  std::vector<std::vector<T>> layers;
-  std::vector<std::vector<fe>> ftrees;
   std::vector<fe> fri_roots;
-  while (ev.size() > rem_max) {
-    const size_t Nd = ev.size(), h = Nd / 2;
-    std::vector<fe> lf(h), row;
-    for (size_t i = 0; i < h; i++) {
-      row.clear();
-      put_flat(row, ev[i]);
-      put_flat(row, ev[i + h]);
-      lf[i] = H.hash_elements(row.data(), row.size());
-    }
-    ftrees.push_back(merkle(lf));
-    fri_roots.push_back(ftrees.back()[1]);
+  for (size_t Nd = N; Nd > rem_max; Nd /= 2) {
+    fri_roots.push_back(be.fri_commit());
     coin.reseed(fri_roots.back());
-    const T a = draw(coin);
-    const fe wd = root_of_unity((unsigned)ilog2(Nd));
-    std::vector<T> nx(h);
-    fe xe = off;
-    for (size_t i = 0; i < h; i++, xe = fe_mul(xe, wd)) {
-      const fe x0 = xe, x1 = fe_sub(fe_zero(), xe);
-      // (v1 (a - x0) - v0 (a - x1)) / (x1 - x0)
-      const T num = sub(mul(ev[i + h], sub(a, lift<T>(x0))), mul(ev[i], sub(a, lift<T>(x1))));
-      nx[i] = mulb(num, fe_inv(fe_sub(x1, x0)));
-    }
-    layers.push_back(std::move(ev));
-    ev = std::move(nx);
+    be.fri_fold(draw(coin));
   }
+  be.finish();
+  const std::vector<std::vector<fe>>& lde = be.lde;
+  const std::vector<std::vector<T>>& clde = be.clde;
+  const std::vector<fe>&ttree = be.ttree, &ctree = be.ctree;
+  const std::vector<std::vector<T>>& layers = be.layers;
+  const std::vector<std::vector<fe>>& ftrees = be.ftrees;
+  const std::vector<T>& ev = be.ev;
   const int nl = (int)layers.size();
   std::vector<T> rco = interpolate(ev, off);
   const size_t rlen = o.fri_remainder_max_degree + 1;
@@ -1372,6 +1380,22 @@ std::vector<Child> load_children(const uint8_t* const* steps, const size_t* lens
       throw AggError("RecursionBackend::recursion_prove requires all steps to share the same suite_id");
   return ch;
 }
+bool canonical_fe(fe v) { return v.hi < P_HI || v.lo < P_LO; }
+
+// Process-wide switch of the device ZlAggAir prover (zkl_hip_set_agg_device_prover): -1 = not
+// read yet, then ZKL_AGG_DEVICE_PROVER=0 in the environment starts it at 0, anything else at 1.
+std::atomic<int> g_agg_device_prover{-1};
+bool agg_device_prover_enabled() {
+  int v = g_agg_device_prover.load();
+  if (v < 0) {
+    const char* e = getenv("ZKL_AGG_DEVICE_PROVER");
+    v = (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+    int expect = -1;
+    if (!g_agg_device_prover.compare_exchange_strong(expect, v)) v = expect;
+  }
+  return v != 0;
+}
+
 AggPi public_of(const std::vector<Child>& ch) {
   std::vector<StepDecoded> st;
   for (const Child& c : ch) st.push_back(c.step);
@@ -1381,7 +1405,9 @@ AggPi public_of(const std::vector<Child>& ch) {
 
 extern "C" {
 
-static int agg_prove_with(const PlanExec& exec, size_t cap, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
+// prover_ctx: the context whose device runs the ZlAggAir proof (nullptr: the host backend)
+static int agg_prove_with(const PlanExec& exec, size_t cap, zkl_ctx* prover_ctx, const uint8_t* const* steps,
+                          const size_t* step_lens, uint32_t n_steps,
                           const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                           uint8_t digest_out[32]) {
   if (!opts || !artifact_out || !artifact_len) return ZKL_E_INVALID;
@@ -1408,8 +1434,10 @@ static int agg_prove_with(const PlanExec& exec, size_t cap, const uint8_t* const
     const std::vector<fe> el = agg_pi_elements(pi);
     ao.check_air = opts->trace_mode == ZKL_AGG_TRACE_VALID;
     t0 = std::chrono::steady_clock::now();
-    const std::vector<uint8_t> proof =
-        ao.field_ext == 2 ? prove_air<fe2>(T, el, pi, ao) : prove_air<fe>(T, el, pi, ao);
+    zkl_ctx* pctx = agg_device_prover_enabled() ? prover_ctx : nullptr;
+    const std::vector<uint8_t> proof = ao.field_ext == 2
+                                           ? prove_air<fe2>(T, el, pi.v_units_total, pi.children_count, ao, pctx)
+                                           : prove_air<fe>(T, el, pi.v_units_total, pi.children_count, ao, pctx);
     g_agg_ms[3] = ms_since(t0) - g_agg_ms[4];
     art = encode_artifact(pi, proof);
     if (digest_out) recursion_digest(pi, digest_out);
@@ -1425,14 +1453,58 @@ static int agg_prove_with(const PlanExec& exec, size_t cap, const uint8_t* const
 
 int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps, const zkl_agg_options* opts,
                   uint8_t** artifact_out, size_t* artifact_len, uint8_t digest_out[32]) {
-  return agg_prove_with(host_plan_exec(), 0, steps, step_lens, n_steps, opts, artifact_out, artifact_len, digest_out);
+  return agg_prove_with(host_plan_exec(), 0, nullptr, steps, step_lens, n_steps, opts, artifact_out, artifact_len,
+                        digest_out);
 }
 
 int zkl_hip_agg_prove(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                       const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                       uint8_t digest_out[32]) {
-  return agg_prove_with(ctx ? device_plan_exec(ctx) : host_plan_exec(), ctx ? PLAN_DEVICE_CAP : 0, steps, step_lens, n_steps, opts, artifact_out,
-                        artifact_len, digest_out);
+  return agg_prove_with(ctx ? device_plan_exec(ctx) : host_plan_exec(), ctx ? PLAN_DEVICE_CAP : 0, ctx, steps, step_lens,
+                        n_steps, opts, artifact_out, artifact_len, digest_out);
+}
+
+int zkl_hip_set_agg_device_prover(int on) {
+  if (on != 0 && on != 1) return ZKL_E_INVALID;
+  g_agg_device_prover.store(on);
+  return ZKL_OK;
+}
+
+int zkl_hip_agg_device_prover(void) { return agg_device_prover_enabled() ? 1 : 0; }
+
+int zkl_hip_agg_prove_trace(zkl_ctx* ctx, const zkl_f128* trace, uint32_t rows, const zkl_f128* pi_elements, uint32_t n_pi,
+                            uint64_t v_units_total, uint32_t children_count, const zkl_agg_options* opts, int check_air,
+                            uint8_t** proof_out, size_t* proof_len) {
+  if (!trace || (!pi_elements && n_pi) || !opts || !proof_out || !proof_len) return ZKL_E_INVALID;
+  std::vector<uint8_t> proof;
+  const int rc = guarded_call([&] {
+    if (rows < MIN_AGG_TRACE_ROWS || rows >= (1u << 14) || (rows & (rows - 1)))
+      throw AggError("aggregation trace rows must be a power of two in [8, 2^14)");
+    AggOpts ao{std::max<uint32_t>(opts->queries, 16), opts->blowup, opts->grind, opts->min_security_bits >= 128 ? 2u : 1u};
+    if (ao.queries > 255) throw AggError("queries must be at most 255");
+    if (ao.grind > 32) throw AggError("grinding factor must be at most 32");
+    ao.check_air = check_air != 0;
+    std::vector<std::vector<fe>> T(AGG_W, std::vector<fe>(rows));
+    for (size_t c = 0; c < AGG_W; c++)
+      for (uint32_t r = 0; r < rows; r++) {
+        const fe v = fe_from(trace[c * rows + r]);
+        if (!canonical_fe(v)) throw AggError("aggregation trace element is not a canonical field element");
+        T[c][r] = v;
+      }
+    std::vector<fe> el(n_pi);
+    for (uint32_t k = 0; k < n_pi; k++) {
+      el[k] = fe_from(pi_elements[k]);
+      if (!canonical_fe(el[k])) throw AggError("public input element is not a canonical field element");
+    }
+    proof = ao.field_ext == 2 ? prove_air<fe2>(T, el, v_units_total, children_count, ao, ctx)
+                              : prove_air<fe>(T, el, v_units_total, children_count, ao, ctx);
+  });
+  if (rc) return rc;
+  *proof_out = (uint8_t*)malloc(proof.size());
+  if (!*proof_out) return ZKL_E_OOM;
+  memcpy(*proof_out, proof.data(), proof.size());
+  *proof_len = proof.size();
+  return ZKL_OK;
 }
 
 int zkl_agg_last_times(double* out_ms, int max_n) {

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/zkl_hip.h"
+#include "agg_ctx.h"
 #include "air_host.h"
 #include "host_hash.h"
 #include "kernels.h"
@@ -191,6 +192,9 @@ struct zkl_ctx {
   DBuf tg;
   hipEvent_t tg_ev = nullptr, tg_t0 = nullptr, tg_t1 = nullptr;  // upload done; timing pair (kernel timing 2)
   bool tg_timed = false;
+  // device ZlAggAir prover (agg.hip): its arrays and pinned staging, by slot
+  DBuf agg_d[AGG_D_SLOTS];
+  HBuf agg_h[AGG_H_SLOTS];
 };
 
 static const char* kFamilyNames =
@@ -1562,6 +1566,25 @@ void run_plans_device(zkl_ctx* C, const HashPlan* const* plans, size_t n, const 
   for (size_t i = 0; i < n; i++) outs[i] = C->h_vout.at<fe>() + out_base[i];
 }
 }  // namespace
+
+// ---- context access of the device ZlAggAir prover (agg_backend.h) ----
+AggCtxView zkl::agg_ctx_begin(zkl_ctx* C) {
+  HIPCHECK(hipSetDevice(C->device));
+  upload_hasher(C->stream);
+  return AggCtxView{C->device, (void*)C->stream};
+}
+void zkl::agg_ctx_lock(zkl_ctx* C) { C->mu.lock(); }
+void zkl::agg_ctx_unlock(zkl_ctx* C) { C->mu.unlock(); }
+void* zkl::agg_ctx_dbuf(zkl_ctx* C, int slot, size_t bytes) {
+  if (slot < 0 || slot >= AGG_D_SLOTS) throw std::logic_error("aggregation device buffer slot");
+  C->agg_d[slot].ensure(std::max<size_t>(bytes, 16));
+  return C->agg_d[slot].p;
+}
+void* zkl::agg_ctx_hbuf(zkl_ctx* C, int slot, size_t bytes) {
+  if (slot < 0 || slot >= AGG_H_SLOTS) throw std::logic_error("aggregation staging buffer slot");
+  C->agg_h[slot].ensure(std::max<size_t>(bytes, 16));
+  return C->agg_h[slot].p;
+}
 
 PlanExec zkl::device_plan_exec(zkl_ctx* ctx) {
   return [ctx](const HashPlan* const* plans, size_t n, const fe** outs) {

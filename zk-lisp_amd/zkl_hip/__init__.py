@@ -17,7 +17,7 @@ __all__ = [
     "select_partitions_for_trace", "proof_options", "synth_vm_segment", "STAGE_NAMES",
     "FM_VM", "FM_VM_EXPECT", "FM_POSEIDON", "FM_SPONGE", "FM_MERKLE", "FM_RAM",
     "VmArg", "StepInfo", "check_request", "row_digest_rule", "verify_segment", "step_proof_encode", "step_proof_digest", "parse_step_proof", "children_root",
-    "AggOptions", "agg_prove", "agg_verify", "agg_trace", "parse_agg_artifact", "synth_segment_chain", "synth_vm_segment_chain",
+    "AggOptions", "agg_prove", "agg_prove_trace", "agg_device_prover", "agg_verify", "agg_trace", "parse_agg_artifact", "synth_segment_chain", "synth_vm_segment_chain",
     "step_info_for", "ZklOp", "op", "build_trace", "OP_KINDS", "rom_acc_from_program", "plan_segments", "slice_segment",
 ]
 
@@ -251,6 +251,10 @@ def load_library():
                                   P(C.c_size_t), C.c_void_p]
     lib.zkl_hip_agg_prove.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_uint32, P(AggOptions),
                                       P(P(C.c_uint8)), P(C.c_size_t), C.c_void_p]
+    lib.zkl_hip_set_agg_device_prover.argtypes = [C.c_int]
+    lib.zkl_hip_agg_device_prover.argtypes = []
+    lib.zkl_hip_agg_prove_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64,
+                                            C.c_uint32, P(AggOptions), C.c_int, P(P(C.c_uint8)), P(C.c_size_t)]
     lib.zkl_agg_last_times.argtypes = [P(C.c_double), C.c_int]
     lib.zkl_hip_verify_segments.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), P(AirPublicInputs),
                                             P(ProofOptions), C.c_uint32, P(C.c_int32), C.c_char_p]
@@ -313,6 +317,62 @@ def agg_prove(steps, queries=64, blowup=16, grind=16, min_security_bits=128, tra
     data = C.string_at(out, ln.value)
     lib.zkl_hip_free(out)
     return data, bytes(dg)
+
+
+def agg_prove_trace(trace, pi_elements, v_units_total, children_count, queries=64, blowup=16, grind=16,
+                    min_security_bits=128, check_air=True, *, ctx=None):
+    """The ZlAggAir proof of a caller's trace, without any child (zkl_hip_agg_prove_trace): the
+    inner proof bytes that end agg_prove's artifact.  trace: 31 column lists of ints, or the
+    column-major bytes (31 x rows little-endian 16-byte elements); pi_elements:
+    AggAirPublicInputs::to_elements as ints; v_units_total / children_count: the two last-row
+    assertion values.  min_security_bits >= 128 selects the quadratic extension and is not
+    otherwise enforced.  check_air False proves any trace.  ctx (a Context): the proof's arrays
+    are computed on its device -- same bytes; None: the host backend."""
+    lib = load_library()
+    if isinstance(trace, (bytes, bytearray, memoryview)):
+        raw = bytes(trace)
+        if len(raw) % (31 * 16):
+            raise ValueError("trace bytes must hold 31 columns of 16-byte elements")
+        rows = len(raw) // (31 * 16)
+        buf = (F128 * (31 * rows)).from_buffer_copy(raw)
+    else:
+        if len(trace) != 31 or any(len(c) != len(trace[0]) for c in trace):
+            raise ValueError("trace must be 31 columns of one length")
+        rows = len(trace[0])
+        m = (1 << 64) - 1
+        buf = (F128 * (31 * rows))(*[F128(v & m, v >> 64) for c in trace for v in c])
+    m = (1 << 64) - 1
+    pe = (F128 * max(len(pi_elements), 1))(*[F128(int(v) & m, int(v) >> 64) for v in pi_elements])
+    o = AggOptions(queries, blowup, grind, min_security_bits, 0)
+    out, ln = C.POINTER(C.c_uint8)(), C.c_size_t()
+    rc = lib.zkl_hip_agg_prove_trace(ctx.ptr if ctx is not None else None, C.cast(buf, C.c_void_p), rows,
+                                     C.cast(pe, C.c_void_p), len(pi_elements), v_units_total, children_count,
+                                     C.byref(o), 1 if check_air else 0, C.byref(out), C.byref(ln))
+    if rc:
+        raise ZklError(rc, lib.zkl_hip_last_error(None).decode(errors="replace"))
+    data = C.string_at(out, ln.value)
+    lib.zkl_hip_free(out)
+    return data
+
+
+class agg_device_prover:
+    """Context manager setting the process-wide switch of the device ZlAggAir prover
+    (zkl_hip_set_agg_device_prover) for the duration of the block: 0 keeps agg_prove(ctx=...)
+    on the host prover while the context's device still hashes the child replays."""
+
+    def __init__(self, on):
+        self.on = 1 if on else 0
+
+    def __enter__(self):
+        lib = load_library()
+        self.prev = lib.zkl_hip_agg_device_prover()
+        if lib.zkl_hip_set_agg_device_prover(self.on) != 0:
+            raise ZklError(-1, "zkl_hip_set_agg_device_prover failed")
+        return self
+
+    def __exit__(self, *a):
+        load_library().zkl_hip_set_agg_device_prover(self.prev)
+        return False
 
 
 AGG_TIME_NAMES = ("replay_host", "replay_hash", "trace", "prove", "grind", "total")
