@@ -633,14 +633,53 @@ int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t
                   uint8_t digest_out[32]);
 /* zkl_agg_prove on ctx's device: the child replay's hashing and the ZlAggAir proof itself (trace
  * LDE, commitments, constraint composition, DEEP and FRI in the proof's field, the quadratic
- * extension included).  The transcript, the AIR pre-check, the out-of-domain frame
- * and grinding stay on the host, so a batch that violates ZlAggAir is rejected before any launch
- * of the prover.  Same arguments, same artifact bytes, same digest, same rejections.  ctx NULL is
+ * extension included), and the proof's grinding (the segment prover's ascending
+ * nonce windows on ctx's stream: the smallest nonce, as the host search finds).  The transcript, the
+ * AIR pre-check and the out-of-domain frame stay on the host, so a batch that violates ZlAggAir is
+ * rejected before any launch of the prover.  Same arguments, same artifact bytes, same digest, same rejections.  ctx NULL is
  * zkl_agg_prove.  Rank 0 of a multi-GPU run holds a context after proving its own segments and
  * can pass it here. */
 int zkl_hip_agg_prove(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                       const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                       uint8_t digest_out[32]);
+/* ---- aggregation session: aggregate while the segments prove ----
+ * zkl_agg_prove / zkl_hip_agg_prove in three steps, so that everything that depends on one child
+ * alone runs when that child's step proof exists rather than after the last one.  For step proofs
+ * st[0..n): begin(ctx, n, opts), add(p, st[p]) for every p in any order and from any number of
+ * threads, then finish, give the artifact and the recursion digest that
+ * zkl_hip_agg_prove(ctx, st, lens, n, opts, ..) gives, byte for byte, in both trace modes and both
+ * field choices; the one-shot calls are this sequence over the same code.  ctx NULL: the host
+ * executor and the host prover (zkl_agg_prove).
+ *   begin   checks the options first (queries above 255, grind above 32, unknown trace mode, the
+ *           conjectured-security check: ZKL_E_INVALID with the one-shot calls' texts) and refuses
+ *           n_steps == 0.  The one-shot calls check the children before the options, so a batch
+ *           that is wrong in both ways is refused with another text there.
+ *   add     copies the bytes, decodes and replays the child (its hashing on the session's
+ *           executor: ctx's device when a context was given), checks its two FRI layers and
+ *           computes the unweighted terms of its aggregation trace row, all before it returns.
+ *           Returns the child's own verdict: ZKL_OK, or ZKL_E_INVALID with the one-shot text
+ *           ("child <position>: child step proof does not replay: ...").  A refused child counts
+ *           as added and does not stop later adds.  A position >= n_steps or added before is
+ *           ZKL_E_INVALID and changes nothing.
+ *   finish  is called once, after every add has returned.  Fewer than n_steps positions added is
+ *           ZKL_E_INVALID ("aggregation session: k of n step proofs added"); otherwise the message
+ *           of the lowest refused position, then the cross-child checks in the one-shot order (the
+ *           shared suite, the batch checks of the trace builder, the AIR pre-check in the valid
+ *           mode), the trace and the ZlAggAir proof on ctx.  The artifact is freed with
+ *           zkl_hip_free.  After finish, whether it succeeded or not, only free is valid.
+ *   times   [0] summed host time of the adds, [1] their summed hashing time, [2] trace assembly in
+ *           finish, [3] the proof without grinding, [4] grinding, [5] the whole of finish (ms).
+ *           Returns the number written.
+ *   free    releases the session, finished or not.
+ * Locking: add takes the context's lock only around its device submission, finish around the
+ * proof's launches.  A context that is also proving segments serialises with them, so a session
+ * that runs beside the segment provers should be given a context of its own. */
+typedef struct zkl_agg_session zkl_agg_session;
+int zkl_hip_agg_begin(zkl_ctx* ctx, uint32_t n_steps, const zkl_agg_options* opts, zkl_agg_session** out);
+int zkl_hip_agg_add(zkl_agg_session* s, uint32_t position, const uint8_t* step, size_t len);
+int zkl_hip_agg_finish(zkl_agg_session* s, uint8_t** artifact_out, size_t* artifact_len, uint8_t digest_out[32]);
+int zkl_hip_agg_session_times(const zkl_agg_session* s, double* out_ms, int max_n);
+void zkl_hip_agg_free(zkl_agg_session* s);
 /* Process-wide switch of the device ZlAggAir prover, default 1 (ZKL_AGG_DEVICE_PROVER=0 in the
  * environment starts it at 0).  0: zkl_hip_agg_prove keeps the host prover while the context's
  * device still hashes the child replays -- same bytes, for A/B runs.  The setter takes 0 or 1

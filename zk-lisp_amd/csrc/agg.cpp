@@ -31,6 +31,7 @@
 #include <chrono>
 #include <exception>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -401,41 +402,26 @@ fe deep_value(const SegmentView& v, size_t k) {
   }
   return y;
 }
-fe deep_agg(const SegmentView& v, fe beta) {
-  fe acc = fe_zero(), bp = fe_one();
-  for (size_t k = 0; k < v.positions.size(); k++) {
-    const fe e = fe_sub(deep_value(v, k), layer_value(v, 0, v.positions[k], v.lde));
-    acc = fe_add(acc, fe_mul(bp, e));
-    bp = fe_mul(bp, beta);
-  }
-  return acc;
-}
-// compute_fri_layer1_agg_over_queries (agg/trace.rs:1261-1432)
-fe fri_layer1_agg(const SegmentView& v, fe beta) {
-  const size_t N = v.lde;
-  const auto& f0 = v.fri_positions[0];
-  fe acc = fe_zero(), bp = fe_one();
-  const size_t nk = std::min(f0.size(), v.positions.size());
-  for (size_t k = 0; k < nk; k++) {
-    const fe vn = fri_fold_at(v.fri_values[0][2 * k], v.fri_values[0][2 * k + 1], v.fri_alphas[0], f0[k], N);
-    acc = fe_add(acc, fe_mul(bp, fe_sub(vn, layer_value(v, 1, f0[k], N / 2))));
-    bp = fe_mul(bp, beta);
-  }
-  return acc;
-}
-// compute_fri_path_agg_over_layers (agg/trace.rs:697-951): one query path through every
-// layer and the remainder (Horner over the reversed coefficients at the constant offset)
-fe fri_path_agg(const SegmentView& v, fe delta, size_t s) {
+// ---- the per-child part of the overlay (trace.rs:187-235, sample_fri_fold_child :1436-1685)
+// The four sums of a child's row are weighted by agg_weights(pi), which hashes the public inputs
+// of all children; their terms depend on the child alone.  child_terms computes the terms when
+// the child arrives (an aggregation session's add), the weigh_* functions apply the weights once
+// every child is known.
+//
+// one query path through every layer and the remainder (compute_fri_path_agg_over_layers,
+// agg/trace.rs:697-951; Horner over the reversed coefficients at the constant offset): the
+// terms in the order delta^0, delta^1, ... weighs them
+std::vector<fe> fri_path_terms(const SegmentView& v, size_t s) {
   const int nl = (int)v.fri_roots.size();
-  fe acc = fe_zero(), dp = fe_one(), v_rem = fe_zero();
+  std::vector<fe> t;
+  fe v_rem = fe_zero();
   size_t size = v.lde, pos_rem = 0;
   for (int d = 0; d < nl; d++) {
     const auto& f = v.fri_positions[d];
     if (s >= f.size()) throw AggError("sample index out of bounds for FRI layer");
     const fe vn = fri_fold_at(v.fri_values[d][2 * s], v.fri_values[d][2 * s + 1], v.fri_alphas[d], f[s], size);
     if (d + 1 < nl) {
-      acc = fe_add(acc, fe_mul(dp, fe_sub(vn, layer_value(v, d + 1, f[s], size / 2))));
-      dp = fe_mul(dp, delta);
+      t.push_back(fe_sub(vn, layer_value(v, d + 1, f[s], size / 2)));
     } else {
       v_rem = vn;
       pos_rem = f[s];
@@ -445,14 +431,54 @@ fe fri_path_agg(const SegmentView& v, fe delta, size_t s) {
   const fe xl = fe_mul(fe{3, 0}, fe_pow64(root_of_unity((unsigned)ilog2(size)), pos_rem));
   fe r = fe_zero();
   for (const fe& c : v.remainder) r = fe_add(fe_mul(r, xl), c);
-  return fe_add(acc, fe_mul(dp, fe_sub(v_rem, r)));
+  t.push_back(fe_sub(v_rem, r));
+  return t;
 }
-fe fri_paths_agg(const SegmentView& v, fe delta, fe beta) {
-  size_t paths = ~(size_t)0;
-  for (const auto& f : v.fri_positions) paths = std::min(paths, f.size());
+struct ChildTerms {
+  fe v0{}, v1{}, vn{}, alpha{}, x0{}, x1{}, q1{};  // the layer-0 sample (no weight)
+  std::vector<fe> deep;                // compute_deep_agg_over_queries (agg/trace.rs:1126-1257): per query
+  std::vector<fe> layer1;              // compute_fri_layer1_agg_over_queries (agg/trace.rs:1261-1432): per query
+  std::vector<fe> path0;               // fri_path_terms of sample 0
+  std::vector<std::vector<fe>> paths;  // fri_path_terms of every sample all layers hold
+  std::exception_ptr err;              // what the overlay of this child throws (met after the batch checks)
+};
+void child_terms(const SegmentView& v, ChildTerms& o) {
+  try {
+    const size_t N = v.lde, y0 = v.fri_positions[0][0];
+    o.v0 = v.fri_values[0][0];
+    o.v1 = v.fri_values[0][1];
+    o.alpha = v.fri_alphas[0];
+    o.vn = fri_fold_at(o.v0, o.v1, o.alpha, y0, N, &o.x0, &o.x1);
+    o.q1 = layer_value(v, 1, y0, N / 2);
+    for (size_t k = 0; k < v.positions.size(); k++)
+      o.deep.push_back(fe_sub(deep_value(v, k), layer_value(v, 0, v.positions[k], v.lde)));
+    const auto& f0 = v.fri_positions[0];
+    const size_t nk = std::min(f0.size(), v.positions.size());
+    for (size_t k = 0; k < nk; k++) {
+      const fe vn = fri_fold_at(v.fri_values[0][2 * k], v.fri_values[0][2 * k + 1], v.fri_alphas[0], f0[k], N);
+      o.layer1.push_back(fe_sub(vn, layer_value(v, 1, f0[k], N / 2)));
+    }
+    o.path0 = fri_path_terms(v, 0);
+    size_t paths = ~(size_t)0;
+    for (const auto& f : v.fri_positions) paths = std::min(paths, f.size());
+    for (size_t k = 0; k < paths; k++) o.paths.push_back(k ? fri_path_terms(v, k) : o.path0);
+  } catch (...) {
+    o.err = std::current_exception();
+  }
+}
+// sum_k w^k t[k]
+fe weigh(const std::vector<fe>& t, fe w) {
+  fe acc = fe_zero(), p = fe_one();
+  for (const fe& x : t) {
+    acc = fe_add(acc, fe_mul(p, x));
+    p = fe_mul(p, w);
+  }
+  return acc;
+}
+fe weigh_paths(const std::vector<std::vector<fe>>& paths, fe delta, fe beta) {
   fe acc = fe_zero(), bp = fe_one();
-  for (size_t k = 0; k < paths; k++) {
-    acc = fe_add(acc, fe_mul(bp, fri_path_agg(v, delta, k)));
+  for (const auto& t : paths) {
+    acc = fe_add(acc, fe_mul(bp, weigh(t, delta)));
     bp = fe_mul(bp, beta);
   }
   return acc;
@@ -460,7 +486,9 @@ fe fri_paths_agg(const SegmentView& v, fe delta, fe beta) {
 
 // build_agg_trace_from_transcripts (agg/trace.rs:155-693): column-major AGG_W x rows, in one of
 // the two trace modes of include/zkl_hip.h (ZKL_AGG_TRACE_VALID / ZKL_AGG_TRACE_REFERENCE)
-std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<Child>& ch, uint32_t mode) {
+// tm[i]: child_terms of ch[i]
+std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<Child>& ch, const std::vector<ChildTerms>& tm,
+                                          uint32_t mode) {
   const size_t nc = ch.size();
   if (nc == 0) throw AggError("AggTrace requires at least one child proof");
   if (p.children_count != nc) throw AggError("AggAirPublicInputs.children_count must match number of children");
@@ -522,36 +550,10 @@ std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<C
   const fe ro0 = fold_bytes32(p.rom_initial[0]), ro1 = fold_bytes32(p.rom_final[0]);
   fe v_acc = fe_zero(), cnt = fe_zero(), pvm{}, pru{}, prs{}, pro{};
   const Weights w = agg_weights(p);
-  // per-child FRI / DEEP overlay (trace.rs:187-235, sample_fri_fold_child :1436-1685): the
-  // layer-0 sample and the four sums depend on one child alone and are most of this function's
-  // time, so they run over the children on host threads, into per-child slots, before the
-  // serial loop that chains the accumulators.  A child's error is kept in its slot and the one
-  // of the lowest child rethrown, as the serial loop would have met it first.
-  struct Overlay { fe v0, v1, vn, alpha, x0, x1, q1, comp, adz, ml0, fll; };
-  std::vector<Overlay> ov(nc);
-  {
-    std::vector<std::exception_ptr> err(nc);
-    parallel_for(nc, [&](size_t i) {
-      try {
-        const SegmentView& v = ch[i].v;
-        Overlay& o = ov[i];
-        const size_t N = v.lde, y0 = v.fri_positions[0][0];
-        o.v0 = v.fri_values[0][0];
-        o.v1 = v.fri_values[0][1];
-        o.alpha = v.fri_alphas[0];
-        o.vn = fri_fold_at(o.v0, o.v1, o.alpha, y0, N, &o.x0, &o.x1);
-        o.q1 = layer_value(v, 1, y0, N / 2);
-        o.comp = deep_agg(v, w.beta_deep);
-        o.adz = fri_layer1_agg(v, w.beta_fri_layer1);
-        o.ml0 = fri_path_agg(v, w.delta_depth, 0);
-        o.fll = fri_paths_agg(v, w.delta_depth, w.beta_paths);
-      } catch (...) {
-        err[i] = std::current_exception();
-      }
-    });
-    for (size_t i = 0; i < nc; i++)
-      if (err[i]) std::rethrow_exception(err[i]);
-  }
+  // the per-child FRI / DEEP terms were computed from each child alone (child_terms); a child's
+  // error there is met here, after the batch checks above, and the one of the lowest child thrown
+  for (size_t i = 0; i < nc; i++)
+    if (tm[i].err) std::rethrow_exception(tm[i].err);
   for (size_t i = 0; i < nc; i++) {
     const StepDecoded& s = ch[i].step;
     const fe vm_in = fold_bytes32(s.bnd[0]), vm_out = fold_bytes32(s.bnd[1]);
@@ -586,7 +588,7 @@ std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<C
     T[C_RAM_U_CHAIN_ERR][i] = ru_err;
     T[C_RAM_S_CHAIN_ERR][i] = rs_err;
     T[C_ROM_CHAIN_ERR_0][i] = ro_err;
-    const Overlay& o = ov[i];
+    const ChildTerms& o = tm[i];
     T[C_FRI_V0][i] = o.v0;
     T[C_FRI_V1][i] = o.v1;
     T[C_FRI_VNEXT][i] = o.vn;
@@ -594,10 +596,10 @@ std::vector<std::vector<fe>> build_agg_trace(const AggPi& p, const std::vector<C
     T[C_FRI_X0][i] = o.x0;
     T[C_FRI_X1][i] = o.x1;
     T[C_FRI_Q1][i] = o.q1;
-    T[C_COMP_SUM][i] = o.comp;
-    T[C_ALPHA_DIV_ZM_SUM][i] = o.adz;
-    T[C_MAP_L0_SUM][i] = o.ml0;
-    T[C_FINAL_LLAST_SUM][i] = o.fll;
+    T[C_COMP_SUM][i] = weigh(o.deep, w.beta_deep);
+    T[C_ALPHA_DIV_ZM_SUM][i] = weigh(o.layer1, w.beta_fri_layer1);
+    T[C_MAP_L0_SUM][i] = weigh(o.path0, w.delta_depth);
+    T[C_FINAL_LLAST_SUM][i] = weigh_paths(o.paths, w.delta_depth, w.beta_paths);
     v_acc = fe_add(v_acc, fe{s.v_units, 0});
     cnt = fe_add(cnt, fe_one());
     pvm = vm_out; pru = ru_out; prs = rs_out; pro = ro_out;
@@ -758,7 +760,8 @@ struct AggHostBackend final : AggBackend<T> {
 // host loops above (ctx == nullptr) or the kernels of agg.hip on ctx's device.
 template <class T>
 std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const std::vector<fe>& pi_el,
-                               uint64_t v_units_total, uint32_t children_count, const AggOpts& ao, zkl_ctx* ctx) {
+                               uint64_t v_units_total, uint32_t children_count, const AggOpts& ao, zkl_ctx* ctx,
+                               double* grind_ms) {
   const Hasher& H = hasher();
   const size_t W = trace.size(), n = trace[0].size();
   const int logn = ilog2(n);
@@ -915,11 +918,12 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   }
   coin.reseed(rem_commit);
 
-  // 7. grinding: smallest nonce >= 1 (host threads; winterfell without `concurrent` searches
-  // sequentially, so the minimum is what it finds)
+  // 7. grinding: smallest nonce >= 1 (winterfell without `concurrent` searches sequentially, so
+  // the minimum is what it finds): the backend's search (the device backend's ascending windows
+  // on the context's stream), else host threads
   uint64_t nonce = 1;
   const auto t_grind = std::chrono::steady_clock::now();
-  if (ao.grind > 0) {
+  if (ao.grind > 0 && !be.grind(coin.seed, ao.grind, &nonce)) {
     const fe sd = coin.seed;
     const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     const uint64_t chunk = 4096;
@@ -944,7 +948,7 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
     for (auto& t : th) t.join();
     nonce = best.load();
   }
-  g_agg_ms[4] = ms_since(t_grind);
+  if (grind_ms) *grind_ms = ms_since(t_grind);
   // 8. query positions: draw_integers(q, N, nonce), sort, dedup
   coin.seed = H.merge_with_int(coin.seed, nonce);
   coin.counter = 0;
@@ -1336,51 +1340,151 @@ std::string verify_artifact(const uint8_t* art, size_t len, uint32_t min_bits) {
 using namespace zkl;
 
 namespace {
-// exec runs the hash plans of the child replays (host threads or a context's device); ms
-// (nullable) accumulates [0] decode + host replay, [1] hashing
-std::vector<Child> load_children(const uint8_t* const* steps, const size_t* lens, uint32_t n, const PlanExec& exec,
-                                 size_t cap, double* ms) {
-  if (!steps || !lens || n == 0) throw AggError("RecursionBackend::recursion_prove requires at least one step proof");
-  for (uint32_t i = 0; i < n; i++)
-    if (!steps[i]) throw AggError("null step proof");
-  // children replay independently (~10^4 permutations each at 2^16 rows): decoded and planned on
-  // host threads, hashed by exec, each replay being verify_segment_ex without the out-of-domain
-  // identity (agg/fs.rs:38-245)
-  std::vector<Child> ch(n);
-  std::vector<std::string> err(n);
-  std::vector<zkl_air_public_inputs> pis(n);
-  const auto t0 = std::chrono::steady_clock::now();
-  parallel_for(n, [&](size_t i) {
+// ---- aggregation session (zkl_hip_agg_begin / _add / _finish; the one-shot calls run one) ----
+// A child is replayed when it arrives: everything that depends on it alone (decode, replay, the
+// replay's hashing, the unweighted overlay terms) happens in add, into the slot of its position;
+// finish does what needs every child (the public inputs, the weights, the chain, the proof).
+struct Session {
+  zkl_ctx* ctx = nullptr;  // nullptr: host executor and host prover
+  zkl_agg_options opts{};
+  uint32_t n = 0;
+  std::mutex mu;  // state, added, finished, ms
+  std::vector<uint8_t> state;  // per position: 0 free, 1 being added, 2 added
+  uint32_t added = 0;
+  bool finished = false;
+  std::vector<std::vector<uint8_t>> bytes;  // StepDecoded::inner points into them
+  std::vector<Child> ch;
+  std::vector<ChildTerms> tm;
+  std::vector<std::string> err;  // per position: "" or why the child is refused
+  // [0] host time of the adds without the overlay terms, [1] their hashing, [2] trace assembly,
+  // [3] proof without grinding, [4] grinding, [5] finish; terms: the overlay terms of the adds
+  double ms[6] = {0, 0, 0, 0, 0, 0}, ms_terms = 0;
+};
+
+// The option checks of RecursionBackend::prove (prove.rs:645-681)
+AggOpts checked_options(const zkl_agg_options& o) {
+  AggOpts ao{std::max<uint32_t>(o.queries, 16), o.blowup, o.grind, o.min_security_bits >= 128 ? 2u : 1u};
+  if (ao.queries > 255) throw AggError("queries must be at most 255");
+  if (ao.grind > 32) throw AggError("grinding factor must be at most 32");  // ProofOptions::new [WF-recall]
+  if (o.trace_mode > ZKL_AGG_TRACE_REFERENCE) throw AggError("unknown aggregation trace mode");
+  if (o.min_security_bits >= 64) {  // prove.rs:664-681
+    if (conjectured_bits(ao.queries, ao.blowup, ao.grind, ao.field_ext) < o.min_security_bits)
+      throw AggError(
+          "aggregation prover options do not achieve requested min_security_bits; increase --queries/--blowup/--grind "
+          "or lower --security-bits");
+  }
+  ao.check_air = o.trace_mode == ZKL_AGG_TRACE_VALID;
+  return ao;
+}
+
+const char* const kNoSteps = "RecursionBackend::recursion_prove requires at least one step proof";
+
+void session_init(Session& S, zkl_ctx* ctx, uint32_t n, const zkl_agg_options& opts) {
+  S.ctx = ctx;
+  S.opts = opts;
+  S.n = n;
+  S.state.assign(n, 0);
+  S.bytes.resize(n);
+  S.ch.resize(n);
+  S.tm.resize(n);
+  S.err.resize(n);
+}
+
+// Adds k children at positions pos[0..k): decode and replay plan on host threads, one batch of
+// hashing through the session's executor (host threads, or the context's device under its lock
+// for the submission alone), the verdicts and the overlay terms.  borrow: the caller's buffers
+// outlive the session's use of them (the one-shot calls), so they are not copied and the device
+// results are read where the context left them (no other thread adds).  A position out of range
+// or taken throws before anything changes.
+void session_add(Session& S, const uint32_t* pos, const uint8_t* const* steps, const size_t* lens, size_t k, bool borrow) {
+  {
+    std::lock_guard<std::mutex> lk(S.mu);
+    if (S.finished) throw AggError("aggregation session: add after finish");
+    for (size_t j = 0; j < k; j++) {
+      if (pos[j] >= S.n)
+        throw AggError("aggregation session: position " + std::to_string(pos[j]) + " is out of range (" +
+                       std::to_string(S.n) + " step proofs)");
+      if (S.state[pos[j]] != 0)
+        throw AggError("aggregation session: position " + std::to_string(pos[j]) + " was already added");
+      for (size_t i = 0; i < j; i++)
+        if (pos[i] == pos[j]) throw AggError("aggregation session: position " + std::to_string(pos[j]) + " given twice");
+    }
+    for (size_t j = 0; j < k; j++) S.state[pos[j]] = 1;
+  }
+  double ms[2] = {0, 0}, ms_terms = 0;
+  // children replay independently (~10^4 permutations each at 2^16 rows): each replay is
+  // verify_segment_ex without the out-of-domain identity (agg/fs.rs:38-245)
+  std::vector<zkl_air_public_inputs> pis(k);
+  auto t0 = std::chrono::steady_clock::now();
+  parallel_for(k, [&](size_t j) {
+    const uint32_t i = pos[j];
     try {
-      ch[i].step = decode_step(steps[i], lens[i]);
-      pis[i] = replay_pi(ch[i].step);
+      const uint8_t* p = steps[j];
+      if (!borrow) {
+        S.bytes[i].assign(steps[j], steps[j] + lens[j]);
+        p = S.bytes[i].data();
+      }
+      S.ch[i].step = decode_step(p, lens[j]);
+      pis[j] = replay_pi(S.ch[i].step);
     } catch (const std::exception& e) {
-      err[i] = e.what();
+      S.err[i] = e.what();
     }
   });
-  if (ms) ms[0] += ms_since(t0);
+  ms[0] += ms_since(t0);
   std::vector<BatchItem> items;
-  std::vector<uint32_t> who;
-  for (uint32_t i = 0; i < n; i++)
-    if (err[i].empty()) {
-      items.push_back({ch[i].step.inner, ch[i].step.inner_len, &pis[i], nullptr, &ch[i].v});
-      who.push_back(i);
+  std::vector<size_t> who;
+  for (size_t j = 0; j < k; j++)
+    if (S.err[pos[j]].empty()) {
+      Child& c = S.ch[pos[j]];
+      items.push_back({c.step.inner, c.step.inner_len, &pis[j], nullptr, &c.v});
+      who.push_back(j);
     }
   std::vector<std::string> verr(items.size());
-  verify_segments_batch(items.data(), items.size(), false, exec, cap, verr.data(), ms);
-  for (size_t k = 0; k < who.size(); k++) {
-    const uint32_t i = who[k];
-    if (!verr[k].empty()) err[i] = "child step proof does not replay: " + verr[k];
-    else if (ch[i].v.fri_roots.size() < 2) err[i] = "AggTrace requires at least two FRI layers per child";
+  // an executor per call: each keeps its results until its next call
+  const PlanExec exec = !S.ctx ? host_plan_exec() : borrow ? device_plan_exec(S.ctx) : device_plan_exec_owned(S.ctx);
+  verify_segments_batch(items.data(), items.size(), false, exec, S.ctx ? PLAN_DEVICE_CAP : 0, verr.data(), ms);
+  for (size_t q = 0; q < who.size(); q++) {
+    const uint32_t i = pos[who[q]];
+    if (!verr[q].empty()) S.err[i] = "child step proof does not replay: " + verr[q];
+    else if (S.ch[i].v.fri_roots.size() < 2) S.err[i] = "AggTrace requires at least two FRI layers per child";
   }
-  for (uint32_t i = 0; i < n; i++)
-    if (!err[i].empty()) throw AggError("child " + std::to_string(i) + ": " + err[i]);
-  for (const Child& c : ch)
-    if (memcmp(c.step.suite, ch[0].step.suite, 32))
-      throw AggError("RecursionBackend::recursion_prove requires all steps to share the same suite_id");
-  return ch;
+  t0 = std::chrono::steady_clock::now();
+  parallel_for(k, [&](size_t j) {
+    if (S.err[pos[j]].empty()) child_terms(S.ch[pos[j]].v, S.tm[pos[j]]);
+  });
+  ms_terms = ms_since(t0);
+  std::lock_guard<std::mutex> lk(S.mu);
+  for (size_t j = 0; j < k; j++) S.state[pos[j]] = 2;
+  S.added += (uint32_t)k;
+  S.ms[0] += ms[0];
+  S.ms[1] += ms[1];
+  S.ms_terms += ms_terms;
 }
-bool canonical_fe(fe v) { return v.hi < P_HI || v.lo < P_LO; }
+
+std::string child_error(const Session& S, uint32_t i) { return "child " + std::to_string(i) + ": " + S.err[i]; }
+
+// every position added; the lowest refused child's message; the shared suite
+void session_children(Session& S) {
+  {
+    std::lock_guard<std::mutex> lk(S.mu);
+    if (S.finished) throw AggError("aggregation session: finish was already called");
+    S.finished = true;
+    if (S.added != S.n)
+      throw AggError("aggregation session: " + std::to_string(S.added) + " of " + std::to_string(S.n) +
+                     " step proofs added");
+  }
+  for (uint32_t i = 0; i < S.n; i++)
+    if (!S.err[i].empty()) throw AggError(child_error(S, i));
+  for (const Child& c : S.ch)
+    if (memcmp(c.step.suite, S.ch[0].step.suite, 32))
+      throw AggError("RecursionBackend::recursion_prove requires all steps to share the same suite_id");
+}
+
+AggPi public_of(const std::vector<Child>& ch) {
+  std::vector<StepDecoded> st;
+  for (const Child& c : ch) st.push_back(c.step);
+  return build_public(st);
+}
 
 // Process-wide switch of the device ZlAggAir prover (zkl_hip_set_agg_device_prover): -1 = not
 // read yet, then ZKL_AGG_DEVICE_PROVER=0 in the environment starts it at 0, anything else at 1.
@@ -1396,73 +1500,132 @@ bool agg_device_prover_enabled() {
   return v != 0;
 }
 
-AggPi public_of(const std::vector<Child>& ch) {
-  std::vector<StepDecoded> st;
-  for (const Child& c : ch) st.push_back(c.step);
-  return build_public(st);
+// the cross-child checks in their order, the trace, the proof, the artifact
+std::vector<uint8_t> session_finish(Session& S, uint8_t digest_out[32]) {
+  const auto t_call = std::chrono::steady_clock::now();
+  struct Total {
+    Session& S;
+    std::chrono::steady_clock::time_point t;
+    ~Total() { S.ms[5] = ms_since(t); }
+  } total{S, t_call};
+  session_children(S);
+  auto t0 = std::chrono::steady_clock::now();
+  const AggPi pi = public_of(S.ch);  // build_public; prove() re-derives suite / count / ms identically
+  const auto T = build_agg_trace(pi, S.ch, S.tm, S.opts.trace_mode);
+  S.ms[2] = ms_since(t0);
+  const AggOpts ao = checked_options(S.opts);
+  const std::vector<fe> el = agg_pi_elements(pi);
+  t0 = std::chrono::steady_clock::now();
+  zkl_ctx* pctx = agg_device_prover_enabled() ? S.ctx : nullptr;
+  const std::vector<uint8_t> proof = ao.field_ext == 2
+                                         ? prove_air<fe2>(T, el, pi.v_units_total, pi.children_count, ao, pctx, &S.ms[4])
+                                         : prove_air<fe>(T, el, pi.v_units_total, pi.children_count, ao, pctx, &S.ms[4]);
+  S.ms[3] = ms_since(t0) - S.ms[4];
+  if (digest_out) recursion_digest(pi, digest_out);
+  return encode_artifact(pi, proof);
 }
+
+// the one-shot calls' argument checks, then every child in one add
+void session_add_all(Session& S, const uint8_t* const* steps, const size_t* lens, uint32_t n) {
+  if (!steps || !lens || n == 0) throw AggError(kNoSteps);
+  for (uint32_t i = 0; i < n; i++)
+    if (!steps[i]) throw AggError("null step proof");
+  std::vector<uint32_t> pos(n);
+  for (uint32_t i = 0; i < n; i++) pos[i] = i;
+  session_add(S, pos.data(), steps, lens, n, true);
+}
+
+int give_bytes(const std::vector<uint8_t>& v, uint8_t** out, size_t* len) {
+  *out = (uint8_t*)malloc(std::max<size_t>(v.size(), 1));
+  if (!*out) return ZKL_E_OOM;
+  memcpy(*out, v.data(), v.size());
+  *len = v.size();
+  return ZKL_OK;
+}
+bool canonical_fe(fe v) { return v.hi < P_HI || v.lo < P_LO; }
+
 }  // namespace
 
 extern "C" {
 
-// prover_ctx: the context whose device runs the ZlAggAir proof (nullptr: the host backend)
-static int agg_prove_with(const PlanExec& exec, size_t cap, zkl_ctx* prover_ctx, const uint8_t* const* steps,
-                          const size_t* step_lens, uint32_t n_steps,
+// the one-shot calls: a session that is begun, given every child at once and finished.  The
+// children are checked before the options here (in a session begin checks the options first).
+static int agg_prove_with(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                           const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                           uint8_t digest_out[32]) {
   if (!opts || !artifact_out || !artifact_len) return ZKL_E_INVALID;
   std::vector<uint8_t> art;
   const auto t_call = std::chrono::steady_clock::now();
   for (double& x : g_agg_ms) x = 0;
+  Session S;
   const int rc = guarded_call([&] {
-    const std::vector<Child> ch = load_children(steps, step_lens, n_steps, exec, cap, g_agg_ms);
-    auto t0 = std::chrono::steady_clock::now();
-    const AggPi pi = public_of(ch);  // build_public; prove() re-derives suite / count / ms identically
-    const auto T = build_agg_trace(pi, ch, opts->trace_mode);
-    g_agg_ms[2] = ms_since(t0);
-    AggOpts ao{std::max<uint32_t>(opts->queries, 16), opts->blowup, opts->grind,
-               opts->min_security_bits >= 128 ? 2u : 1u};
-    if (ao.queries > 255) throw AggError("queries must be at most 255");
-    if (ao.grind > 32) throw AggError("grinding factor must be at most 32");  // ProofOptions::new [WF-recall]
-    if (opts->trace_mode > ZKL_AGG_TRACE_REFERENCE) throw AggError("unknown aggregation trace mode");
-    if (opts->min_security_bits >= 64) {  // prove.rs:664-681
-      if (conjectured_bits(ao.queries, ao.blowup, ao.grind, ao.field_ext) < opts->min_security_bits)
-        throw AggError(
-            "aggregation prover options do not achieve requested min_security_bits; increase --queries/--blowup/--grind "
-            "or lower --security-bits");
-    }
-    const std::vector<fe> el = agg_pi_elements(pi);
-    ao.check_air = opts->trace_mode == ZKL_AGG_TRACE_VALID;
-    t0 = std::chrono::steady_clock::now();
-    zkl_ctx* pctx = agg_device_prover_enabled() ? prover_ctx : nullptr;
-    const std::vector<uint8_t> proof = ao.field_ext == 2
-                                           ? prove_air<fe2>(T, el, pi.v_units_total, pi.children_count, ao, pctx)
-                                           : prove_air<fe>(T, el, pi.v_units_total, pi.children_count, ao, pctx);
-    g_agg_ms[3] = ms_since(t0) - g_agg_ms[4];
-    art = encode_artifact(pi, proof);
-    if (digest_out) recursion_digest(pi, digest_out);
+    session_init(S, ctx, n_steps, *opts);
+    session_add_all(S, steps, step_lens, n_steps);
+    art = session_finish(S, digest_out);
   });
+  g_agg_ms[0] = S.ms[0];
+  g_agg_ms[1] = S.ms[1];
+  g_agg_ms[2] = S.ms[2] + S.ms_terms;  // the overlay terms are part of the trace in this call's slots
+  g_agg_ms[3] = S.ms[3];
+  g_agg_ms[4] = S.ms[4];
   g_agg_ms[5] = ms_since(t_call);
   if (rc) return rc;
-  *artifact_out = (uint8_t*)malloc(art.size());
-  if (!*artifact_out) return ZKL_E_OOM;
-  memcpy(*artifact_out, art.data(), art.size());
-  *artifact_len = art.size();
-  return ZKL_OK;
+  return give_bytes(art, artifact_out, artifact_len);
 }
 
 int zkl_agg_prove(const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps, const zkl_agg_options* opts,
                   uint8_t** artifact_out, size_t* artifact_len, uint8_t digest_out[32]) {
-  return agg_prove_with(host_plan_exec(), 0, nullptr, steps, step_lens, n_steps, opts, artifact_out, artifact_len,
-                        digest_out);
+  return agg_prove_with(nullptr, steps, step_lens, n_steps, opts, artifact_out, artifact_len, digest_out);
 }
 
 int zkl_hip_agg_prove(zkl_ctx* ctx, const uint8_t* const* steps, const size_t* step_lens, uint32_t n_steps,
                       const zkl_agg_options* opts, uint8_t** artifact_out, size_t* artifact_len,
                       uint8_t digest_out[32]) {
-  return agg_prove_with(ctx ? device_plan_exec(ctx) : host_plan_exec(), ctx ? PLAN_DEVICE_CAP : 0, ctx, steps, step_lens,
-                        n_steps, opts, artifact_out, artifact_len, digest_out);
+  return agg_prove_with(ctx, steps, step_lens, n_steps, opts, artifact_out, artifact_len, digest_out);
 }
+
+int zkl_hip_agg_begin(zkl_ctx* ctx, uint32_t n_steps, const zkl_agg_options* opts, zkl_agg_session** out) {
+  if (!opts || !out) return ZKL_E_INVALID;
+  *out = nullptr;
+  return guarded_call([&] {
+    checked_options(*opts);
+    if (n_steps == 0) throw AggError(kNoSteps);
+    std::unique_ptr<Session> S(new Session());
+    session_init(*S, ctx, n_steps, *opts);
+    *out = reinterpret_cast<zkl_agg_session*>(S.release());
+  });
+}
+
+int zkl_hip_agg_add(zkl_agg_session* s, uint32_t position, const uint8_t* step, size_t len) {
+  if (!s) return ZKL_E_INVALID;
+  Session& S = *reinterpret_cast<Session*>(s);
+  return guarded_call([&] {
+    if (!step) throw AggError("null step proof");
+    session_add(S, &position, &step, &len, 1, false);
+    if (!S.err[position].empty()) throw AggError(child_error(S, position));
+  });
+}
+
+int zkl_hip_agg_finish(zkl_agg_session* s, uint8_t** artifact_out, size_t* artifact_len, uint8_t digest_out[32]) {
+  if (!s || !artifact_out || !artifact_len) return ZKL_E_INVALID;
+  Session& S = *reinterpret_cast<Session*>(s);
+  std::vector<uint8_t> art;
+  const int rc = guarded_call([&] { art = session_finish(S, digest_out); });
+  if (rc) return rc;
+  return give_bytes(art, artifact_out, artifact_len);
+}
+
+int zkl_hip_agg_session_times(const zkl_agg_session* s, double* out_ms, int max_n) {
+  if (!s || !out_ms || max_n <= 0) return 0;
+  Session& S = *const_cast<Session*>(reinterpret_cast<const Session*>(s));
+  std::lock_guard<std::mutex> lk(S.mu);
+  const double v[6] = {S.ms[0] + S.ms_terms, S.ms[1], S.ms[2], S.ms[3], S.ms[4], S.ms[5]};
+  const int k = std::min(max_n, 6);
+  for (int i = 0; i < k; i++) out_ms[i] = v[i];
+  return k;
+}
+
+void zkl_hip_agg_free(zkl_agg_session* s) { delete reinterpret_cast<Session*>(s); }
 
 int zkl_hip_set_agg_device_prover(int on) {
   if (on != 0 && on != 1) return ZKL_E_INVALID;
@@ -1496,8 +1659,8 @@ int zkl_hip_agg_prove_trace(zkl_ctx* ctx, const zkl_f128* trace, uint32_t rows, 
       el[k] = fe_from(pi_elements[k]);
       if (!canonical_fe(el[k])) throw AggError("public input element is not a canonical field element");
     }
-    proof = ao.field_ext == 2 ? prove_air<fe2>(T, el, v_units_total, children_count, ao, ctx)
-                              : prove_air<fe>(T, el, v_units_total, children_count, ao, ctx);
+    proof = ao.field_ext == 2 ? prove_air<fe2>(T, el, v_units_total, children_count, ao, ctx, &g_agg_ms[4])
+                              : prove_air<fe>(T, el, v_units_total, children_count, ao, ctx, &g_agg_ms[4]);
   });
   if (rc) return rc;
   *proof_out = (uint8_t*)malloc(proof.size());
@@ -1531,8 +1694,13 @@ int zkl_agg_trace_mode(const uint8_t* const* steps, const size_t* step_lens, uin
                        zkl_f128* out, uint32_t max_rows, uint32_t* rows_out) {
   if (!rows_out || trace_mode > ZKL_AGG_TRACE_REFERENCE) return ZKL_E_INVALID;
   return guarded_call([&] {
-    const std::vector<Child> ch = load_children(steps, step_lens, n_steps, host_plan_exec(), 0, nullptr);
-    const auto T = build_agg_trace(public_of(ch), ch, trace_mode);
+    Session S;
+    zkl_agg_options o{};
+    o.trace_mode = trace_mode;
+    session_init(S, nullptr, n_steps, o);
+    session_add_all(S, steps, step_lens, n_steps);
+    session_children(S);
+    const auto T = build_agg_trace(public_of(S.ch), S.ch, S.tm, trace_mode);
     const uint32_t rows = (uint32_t)T[0].size();
     *rows_out = rows;
     if (!out) return;

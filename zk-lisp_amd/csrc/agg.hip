@@ -11,8 +11,10 @@
 // the flattened E row the commitment hashes.  FRI layer of Nd points, h = Nd / 2: 2 X columns
 // of h rows (lo.a, lo.b, hi.a, hi.b) with lo = e_i, hi = e_{i+h}, so row i is the leaf
 // (e_i, e_{i+h}) flattened.  All three go to launch_hash_rows as one-partition matrices.
+#include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 
 #include "agg_backend.h"
@@ -392,6 +394,44 @@ struct AggDeviceBackend final : AggBackend<T> {
       this->ev = unlayer(h.data() + cur_off, cur_Nd);
     }
     unlock();
+  }
+
+  // The segment prover's nonce search (prover.cpp, step 7) on the context's stream: ascending
+  // windows of 2^g, 2^g, 2^(g+1), 2^(g+2) tries per read-back, a window's kernel returning at
+  // once when an earlier window holds a solution, so the minimum over the first window with one
+  // is the smallest nonce -- what the host search finds.  The coin's seed is a host value in the
+  // form the kernels take by argument.  finish() released the context; it is taken again here.
+  bool grind(fe seed, uint32_t bits, uint64_t* nonce) override {
+    if (bits == 0) {  // the first candidate
+      *nonce = 1;
+      return true;
+    }
+    agg_ctx_lock(C);
+    locked = true;
+    s = (hipStream_t)agg_ctx_begin(C).stream;
+    unsigned long long* d_best = dbuf<unsigned long long>(AGG_D_BEST, 2);
+    unsigned long long* h_best = (unsigned long long*)agg_ctx_hbuf(C, AGG_H_DOWN, 16);
+    uint32_t batch = 1u << std::min<uint32_t>(std::max<uint32_t>(bits, 14), 22);
+    // test-only, as in the segment prover: a small first window makes a test take more than one
+    // window and more than one read-back
+    if (const char* e = getenv("ZKL_TEST_GRIND_FIRST")) batch = (uint32_t)std::max(1L, std::min(atol(e), 1L << 22));
+    uint64_t base = 1;
+    for (;;) {
+      *h_best = ~0ull;
+      ZKL_HIPCHECK(hipMemcpyAsync(d_best, h_best, 8, hipMemcpyHostToDevice, s));
+      for (int w = 0; w < 4; w++) {
+        launch_grind(seed, base, batch, bits, d_best, s, nullptr);
+        base += batch;
+        if (w >= 1) batch = std::min<uint32_t>(batch * 2, 1u << 22);
+      }
+      check_launch("aggregation grinding");
+      ZKL_HIPCHECK(hipMemcpyAsync(h_best, d_best, 8, hipMemcpyDeviceToHost, s));
+      ZKL_HIPCHECK(hipStreamSynchronize(s));
+      if (*h_best != ~0ull) break;
+    }
+    *nonce = *h_best;
+    unlock();
+    return true;
   }
 };
 

@@ -49,6 +49,13 @@ struct AggBackend {
   virtual void fri_fold(T alpha) = 0;
   // everything above is in the host-side members
   virtual void finish() = 0;
+  // 7. grinding after finish(): the smallest nonce >= 1 whose merge_with_int(seed, nonce) has at
+  // least `bits` trailing zero bits.  false: this backend has no search, the skeleton's host
+  // threads run it.
+  virtual bool grind(fe seed, uint32_t bits, uint64_t* nonce) {
+    (void)seed; (void)bits; (void)nonce;
+    return false;
+  }
 };
 
 template <class T>

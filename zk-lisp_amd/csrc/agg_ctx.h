@@ -10,7 +10,7 @@ namespace zkl {
 
 enum AggDBufSlot {
   AGG_D_TRACE, AGG_D_TCOEF, AGG_D_LDE, AGG_D_TTREE, AGG_D_CEV, AGG_D_CCOEF, AGG_D_CLDE, AGG_D_CTREE, AGG_D_FRI,
-  AGG_D_FTREE, AGG_D_ROOTS, AGG_D_CONST, AGG_D_SLOTS
+  AGG_D_FTREE, AGG_D_ROOTS, AGG_D_CONST, AGG_D_BEST, AGG_D_SLOTS
 };
 enum AggHBufSlot { AGG_H_UP, AGG_H_DOWN, AGG_H_SLOTS };
 struct AggCtxView {

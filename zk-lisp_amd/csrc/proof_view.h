@@ -175,6 +175,9 @@ std::string finish_replay(SegmentReplay& R, const fe* out);
 using PlanExec = std::function<void(const HashPlan* const* plans, size_t n, const fe** outs)>;
 PlanExec host_plan_exec();
 PlanExec device_plan_exec(zkl_ctx* ctx);
+// the same, with the results copied out of the context under its lock: outs stay valid until this
+// executor's next call whatever other threads submit to the context meanwhile
+PlanExec device_plan_exec_owned(zkl_ctx* ctx);
 // f(i) for i < n on at most 16 host threads; the first exception is rethrown after the join
 void parallel_for(size_t n, const std::function<void(size_t)>& f);
 

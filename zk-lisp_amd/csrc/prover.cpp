@@ -1593,6 +1593,25 @@ PlanExec zkl::device_plan_exec(zkl_ctx* ctx) {
   };
 }
 
+// device_plan_exec for callers that share the context with other threads: the results leave the
+// context's pinned read-back buffer before the lock is released, into storage the executor owns.
+PlanExec zkl::device_plan_exec_owned(zkl_ctx* ctx) {
+  auto keep = std::make_shared<std::vector<fe>>();
+  return [ctx, keep](const HashPlan* const* plans, size_t n, const fe** outs) {
+    size_t tot = 0;
+    for (size_t i = 0; i < n; i++) tot += plans[i]->n_out;
+    keep->resize(std::max<size_t>(tot, 1));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    run_plans_device(ctx, plans, n, outs);
+    fe* at = keep->data();
+    for (size_t i = 0; i < n; i++) {
+      if (plans[i]->n_out) memcpy(at, outs[i], (size_t)plans[i]->n_out * sizeof(fe));
+      outs[i] = at;
+      at += plans[i]->n_out;
+    }
+  };
+}
+
 // ====================================================================== C ABI
 extern "C" {
 

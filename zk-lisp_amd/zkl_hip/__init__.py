@@ -17,7 +17,7 @@ __all__ = [
     "select_partitions_for_trace", "proof_options", "synth_vm_segment", "STAGE_NAMES",
     "FM_VM", "FM_VM_EXPECT", "FM_POSEIDON", "FM_SPONGE", "FM_MERKLE", "FM_RAM",
     "VmArg", "StepInfo", "check_request", "row_digest_rule", "verify_segment", "step_proof_encode", "step_proof_digest", "parse_step_proof", "children_root",
-    "AggOptions", "agg_prove", "agg_prove_trace", "agg_device_prover", "agg_verify", "agg_trace", "parse_agg_artifact", "synth_segment_chain", "synth_vm_segment_chain",
+    "AggOptions", "AggSession", "agg_prove", "agg_prove_trace", "agg_device_prover", "agg_verify", "agg_trace", "parse_agg_artifact", "synth_segment_chain", "synth_vm_segment_chain",
     "step_info_for", "ZklOp", "op", "build_trace", "OP_KINDS", "rom_acc_from_program", "plan_segments", "slice_segment",
 ]
 
@@ -251,6 +251,12 @@ def load_library():
                                   P(C.c_size_t), C.c_void_p]
     lib.zkl_hip_agg_prove.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_uint32, P(AggOptions),
                                       P(P(C.c_uint8)), P(C.c_size_t), C.c_void_p]
+    lib.zkl_hip_agg_begin.argtypes = [C.c_void_p, C.c_uint32, P(AggOptions), P(C.c_void_p)]
+    lib.zkl_hip_agg_add.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t]
+    lib.zkl_hip_agg_finish.argtypes = [C.c_void_p, P(P(C.c_uint8)), P(C.c_size_t), C.c_void_p]
+    lib.zkl_hip_agg_session_times.argtypes = [C.c_void_p, P(C.c_double), C.c_int]
+    lib.zkl_hip_agg_free.argtypes = [C.c_void_p]
+    lib.zkl_hip_agg_free.restype = None
     lib.zkl_hip_set_agg_device_prover.argtypes = [C.c_int]
     lib.zkl_hip_agg_device_prover.argtypes = []
     lib.zkl_hip_agg_prove_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64,
@@ -317,6 +323,76 @@ def agg_prove(steps, queries=64, blowup=16, grind=16, min_security_bits=128, tra
     data = C.string_at(out, ln.value)
     lib.zkl_hip_free(out)
     return data, bytes(dg)
+
+
+class AggSession:
+    """agg_prove in steps (zkl_hip_agg_begin / _add / _finish): a child is decoded, replayed and
+    hashed when it is added, so the work that depends on one child alone overlaps the proving of
+    the others.  add(position, step) for every position below n_steps, in any order and from any
+    number of threads, then finish() -> (artifact, digest): the bytes agg_prove gives for the same
+    steps and options.  ctx (a Context): the replay hashing and the ZlAggAir proof run on its
+    device; a context that also proves segments serialises with them, so give the session its own.
+    The options are checked here (ZklError); add raises ZklError with the child's own verdict and
+    the session goes on; finish repeats the lowest refused position.  Also a context manager."""
+
+    def __init__(self, n_steps, ctx=None, queries=64, blowup=16, grind=16, min_security_bits=128,
+                 trace_mode=AGG_TRACE_VALID):
+        self._lib = load_library()
+        self._ctx = ctx  # kept alive as long as the session
+        self.n_steps = n_steps
+        self.ptr = None
+        o = AggOptions(queries, blowup, grind, min_security_bits, trace_mode)
+        out = C.c_void_p()
+        rc = self._lib.zkl_hip_agg_begin(ctx.ptr if ctx is not None else None, n_steps, C.byref(o), C.byref(out))
+        if rc:
+            raise ZklError(rc, self._lib.zkl_hip_last_error(None).decode(errors="replace"))
+        self.ptr = out
+
+    def _live(self):
+        if self.ptr is None:
+            raise ZklError(-1, "aggregation session is closed")
+        return self.ptr
+
+    def add(self, position: int, step: bytes) -> None:
+        step = bytes(step)
+        rc = self._lib.zkl_hip_agg_add(self._live(), position, step, len(step))
+        if rc:
+            raise ZklError(rc, self._lib.zkl_hip_last_error(None).decode(errors="replace"))
+
+    def finish(self):
+        out, ln, dg = C.POINTER(C.c_uint8)(), C.c_size_t(), (C.c_uint8 * 32)()
+        rc = self._lib.zkl_hip_agg_finish(self._live(), C.byref(out), C.byref(ln), dg)
+        if rc:
+            raise ZklError(rc, self._lib.zkl_hip_last_error(None).decode(errors="replace"))
+        data = C.string_at(out, ln.value)
+        self._lib.zkl_hip_free(out)
+        return data, bytes(dg)
+
+    def times(self):
+        """Wall times (ms) in the order of AGG_TIME_NAMES (zkl_hip_agg_session_times): the summed
+        host time of the adds, their summed hashing time, then finish's trace assembly, proof
+        without grinding, grinding, and the whole of finish."""
+        v = (C.c_double * 6)()
+        k = self._lib.zkl_hip_agg_session_times(self._live(), v, 6)
+        return [v[i] for i in range(k)]
+
+    def close(self):
+        if self.ptr is not None:
+            self._lib.zkl_hip_agg_free(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
 
 
 def agg_prove_trace(trace, pi_elements, v_units_total, children_count, queries=64, blowup=16, grind=16,

@@ -205,6 +205,52 @@ def gather_step_bytes(step_bytes, comm=None):
     return gather_to_root(list(step_bytes))
 
 
+def feed_rounds(rounds, session, comm=None):
+    """The aggregation hand-off in rounds: `rounds` is an iterable of lists of (segment_index,
+    step_bytes) that this rank produced since the last round; every rank makes the same number of
+    rounds, and a round may be empty.  Each round is one gather_step_bytes with the index packed
+    (u32, little-endian) in front of each blob.  Rank 0 adds what arrives to `session` (an
+    AggSession) on a worker thread, so the proving that produces its next round overlaps the
+    replay of this one; it joins the worker before it returns the number of step proofs added and
+    raises the first error an add gave.  The other ranks pass session=None and return None."""
+    import queue
+    import threading
+    rank, _, _ = env()
+    q, errors, count = queue.Queue(), [], [0]
+
+    def feed():
+        while True:
+            item = q.get()
+            if item is None:
+                return
+            for blob in item:
+                (index,) = struct.unpack_from("<I", blob, 0)
+                try:
+                    session.add(index, blob[4:])
+                    count[0] += 1
+                except Exception as e:  # noqa: BLE001  (raised after the join)
+                    errors.append(e)
+
+    worker = None
+    if rank == 0:
+        worker = threading.Thread(target=feed)
+        worker.start()
+    try:
+        for produced in rounds:
+            got = gather_step_bytes([struct.pack("<I", i) + bytes(b) for i, b in produced], comm)
+            if worker is not None:
+                q.put([b for per_rank in got for b in per_rank])
+    finally:
+        if worker is not None:
+            q.put(None)
+            worker.join()
+    if rank != 0:
+        return None
+    if errors:
+        raise errors[0]
+    return count[0]
+
+
 def collect_step_proofs(step_bytes, comm=None):
     """Aggregation hand-off: every rank contributes the ZKLSTP1 encodings of
     the step proofs it produced; rank 0 receives all of them, decodes each one

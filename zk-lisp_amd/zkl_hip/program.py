@@ -17,9 +17,9 @@ from __future__ import annotations
 
 import threading
 import time
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import ThreadPoolExecutor, wait
 
-from . import Context, Program, proof_options, step_info_for, step_proof_encode
+from . import AGG_TRACE_VALID, AggSession, Context, Program, ZklError, proof_options, step_info_for, step_proof_encode
 
 
 class SegmentProof:
@@ -122,7 +122,74 @@ def prove_program(program: Program, plan, device: int = 0, inflight: int = 4, bu
     return out
 
 
+def step_of(r, total: int, main_args=()):
+    """The zl1 step proof (ZKLSTP1) of one proved segment (prove.rs:1144-1174)."""
+    return step_proof_encode(r.pi, step_info_for(r.pi, r.index, total, r.state_in, r.state_out, main_args=main_args),
+                             r.proof)
+
+
 def steps_of(records, total: int, main_args=()):
     """The zl1 step proofs (ZKLSTP1) of proved segments, in index order (prove.rs:1144-1174)."""
-    return [step_proof_encode(r.pi, step_info_for(r.pi, r.index, total, r.state_in, r.state_out, main_args=main_args),
-                              r.proof) for r in sorted(records, key=lambda r: r.index)]
+    return [step_of(r, total, main_args) for r in sorted(records, key=lambda r: r.index)]
+
+
+def prove_chain(program: Program, plan, device: int = 0, inflight: int = 4, builders: int = 8, queries: int = 64,
+                blowup: int = 16, grind: int = 16, contexts=None, preflight: bool = False, device_build: bool = False,
+                main_args=(), agg_ctx=None, min_security_bits: int = 128, trace_mode: int = AGG_TRACE_VALID,
+                agg_queries=None, agg_blowup=None, agg_grind=None, adders: int = 2):
+    """`zk-lisp prove` as one operation (prove_chain, recursion.rs:203-213): every segment of
+    `plan` proved by prove_program while an aggregation session replays each step proof as soon
+    as it exists (on_proof hands the record to one of `adders` threads, which encodes the step and
+    adds it at the record's index), then the session's finish.  The session runs on agg_ctx, or on
+    a context opened here for it on `device`, so its device work queues beside the segment
+    provers' instead of taking their locks.  A child the session refuses does not stop the
+    proving; finish raises ZklError for the lowest refused position.  queries /
+    blowup / grind are the options of the segment proofs and, unless agg_queries / agg_blowup /
+    agg_grind say otherwise, of the aggregation proof (the CLI passes one set to both).
+    Returns a dict: artifact, digest, steps (index order), times (AggSession.times()) and
+    tail_ms, from the return of the last segment proof to the return of finish."""
+    total = len(plan)
+    own = agg_ctx is None
+    actx = Context(device) if own else agg_ctx
+    steps = [None] * total
+    last = [0.0]
+    lock = threading.Lock()
+    # the adds run on threads of their own, so a context goes on to its next segment while the
+    # step it just proved is replayed (a 2^16-row child is several ms of host work)
+    adders = ThreadPoolExecutor(max_workers=max(1, adders))
+    pending = []
+    try:
+        with AggSession(total, ctx=actx, queries=queries if agg_queries is None else agg_queries,
+                        blowup=blowup if agg_blowup is None else agg_blowup,
+                        grind=grind if agg_grind is None else agg_grind, min_security_bits=min_security_bits,
+                        trace_mode=trace_mode) as session:
+            def add(rec):
+                step = step_of(rec, total, main_args)
+                steps[rec.index] = step
+                try:
+                    session.add(rec.index, step)
+                except ZklError:  # the child's own verdict: finish repeats the lowest refused position
+                    pass
+
+            def on_proof(rec):
+                t = time.perf_counter()
+                with lock:
+                    last[0] = max(last[0], t)
+                    pending.append(adders.submit(add, rec))
+
+            try:
+                prove_program(program, plan, device=device, inflight=inflight, builders=builders, queries=queries,
+                              blowup=blowup, grind=grind, contexts=contexts, on_proof=on_proof, preflight=preflight,
+                              device_build=device_build)
+            finally:  # no add may outlive the session
+                wait(pending)
+            for f in pending:
+                f.result()
+            artifact, digest = session.finish()
+            tail_ms = (time.perf_counter() - last[0]) * 1e3
+            times = session.times()
+    finally:
+        adders.shutdown(wait=True)
+        if own:
+            actx.close()
+    return {"artifact": artifact, "digest": digest, "steps": steps, "times": times, "tail_ms": tail_ms}
