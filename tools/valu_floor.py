@@ -12,14 +12,21 @@ with every non-arithmetic instruction (moves, selects, address arithmetic, waits
 
   cube      square: 5 v_mad_u64_u32 squares + 10 cross products on doubled limbs (+4 shifts)
             multiply: 25 v_mad_u64_u32
-            2 x REDC130: per digit (5): m = col & M26, col+1 += col >> 26 (64-bit shift + add),
-            col+1 += m * 45*2^14, col+4 -= m * 2^24 (2 mads); bias: 3 64-bit adds; output: 4
-            sequential carries (and, 64-bit shift, add)
-  fold      5 neighbouring-digit pairs in 32 bits, 10 v_mad_i64_i32, 4 carries, the 2^128 fold
-            (top * (2^26 - 1) + top * 737279 2^26: 2 mads, 2 shifts/ands, 2 adds)
+            2 x REDC130 as one multiply-add chain per column (mont26.h, redc130_chain): a column
+            opens with the carry of the one below (col >> 26: 8 64-bit shifts and a last 32-bit
+            funnel shift), so no carry is added; per digit (5) m = col & M26 and 2 mads
+            (m * 45*2^14, m * -2^24); 4 output masks; the bias rides on two multiplicands (2 32-bit
+            adds) and the last limb (1)
+  fold      5 neighbouring-digit pairs in 32 bits, 10 v_mad_i64_i32, no carry chain: 4 masks and
+            4 funnel shifts of the columns, the mask and top of column 4, 4 limb adds, the 2^128
+            fold (top * (2^26 - 1) + top * 737279 2^26: 2 mads, 2 funnel shifts, 2 masks)
   pack      4 words of 2 funnel shifts/ors, 4 xors, 1 shift (top)
 
-    python tools/valu_floor.py > profiles/r03/valu_floor.json
+Before round 10 the REDC added each carry to the column's products with a 64-bit add, took three
+64-bit adds for the bias and ran a sequential carry through the fold; that count is
+profiles/r03/valu_floor.json (168 per element and round), which bench.py still reads.
+
+    python tools/valu_floor.py > profiles/r10/valu_floor.json
 """
 import json
 import os
@@ -27,7 +34,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MADBENCH = os.path.join(ROOT, "profiles", "r01", "madbench.txt")
-MIX = os.path.join(ROOT, "profiles", "r02", "valu_mix.json")
+MIX = os.path.join(ROOT, "profiles", "r10", "carry", "valu_mix_build.json")
 
 
 def rates():
@@ -42,12 +49,12 @@ def rates():
 def main():
     R = rates()
     mad, alu64, alu32 = R["v_mad_u64_u32"], R["v_lshl_add_u64"], R["v_add_u32"]
-    redc = {"mad": 2 * 5, "alu64": 2 * 5 + 3 + 4 * 2, "alu32": 5 + 4}
+    redc = {"mad": 2 * 5, "alu64": 8, "alu32": 1 + 5 + 4 + 2 + 1}
     ops = {
         "cube_square": {"mad": 15, "alu32": 4},
         "cube_multiply": {"mad": 25},
         "cube_redc_x2": {k: 2 * v for k, v in redc.items()},
-        "fold": {"mad": 10 + 2, "alu32": 5 + 4 + 4, "alu64": 4 + 2},
+        "fold": {"mad": 10 + 2, "alu32": 5 + (4 + 4) + 2 + 4 + (2 + 2)},
         "pack": {"alu32": 4 * 2 + 4 + 1},
     }
     tot = {"mad": 0, "alu64": 0, "alu32": 0}

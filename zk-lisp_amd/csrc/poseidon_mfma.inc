@@ -30,7 +30,7 @@ typedef int pm_v16i __attribute__((ext_vector_type(16)));
 
 struct PmTables {
   int8_t afrag[6][7][64][16];  // A fragment of tile t, k-step s, lane
-  uint64_t rk[27][12][5];      // limb columns of rc[r][i]*R + K_i (canonical) + p*2^15
+  uint64_t rk[27][12][5];      // limb columns of rc[r][i]*R + K_i (canonical) + p*2^15 + PM_NORM_B terms
 };
 __device__ PmTables d_pm;
 
@@ -146,6 +146,12 @@ static void pm_build(const HasherConsts& h, PmTables& T, Pm16Tables& T16) {
   bias[0] = (uint64_t)((P & 0x7FF) << 15);
   for (int t = 1; t < 4; t++) bias[t] = (uint64_t)((P >> (26 * t - 15)) & M26);
   bias[4] = (uint64_t)(P >> 89);
+  // and PM_NORM_B on columns 0..3, taken back from the next column: every column of
+  // pm_normalise stays non-negative, so that its carries are 32-bit (bounds in mont26.h)
+  for (int t = 0; t < 4; t++) {
+    bias[t] += PM_NORM_B;
+    bias[t + 1] -= PM_NORM_B >> 26;
+  }
   for (int i = 0; i < 12; i++) {
     fe rs = fe_zero();
     for (int k = 0; k < 12; k++) rs = fe_add(rs, h.mds[i * 12 + k]);
@@ -209,57 +215,11 @@ __device__ __forceinline__ void pm_load_tables(PmTables* tb) {
   __syncthreads();
 }
 
-// digit-column sums of one element (+ its round-constant columns) -> 26-bit limbs of a
-// value < 2^129 congruent to it.  Each digit pair (or lone digit) enters its limb column with
-// one v_mad_i64_i32 (the shift as an opaque SGPR multiplier: a constant would become
-// sign-extend + shift + add).
-struct PmShifts {  // 2^s as opaque SGPR multipliers (set once per permutation)
-  int32_t k0, k2, k4, k6, k16, k18, k20, k22;
-};
-__device__ __forceinline__ PmShifts pm_shifts() {
-  PmShifts K{1, 4, 16, 64, 65536, 262144, 1048576, 4194304};
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+s"(K.k0), "+s"(K.k2), "+s"(K.k4), "+s"(K.k6), "+s"(K.k16), "+s"(K.k18), "+s"(K.k20), "+s"(K.k22));
-#endif
-  return K;
-}
+// PmShifts, pm_shifts and pm_normalise (digit-column sums + round-constant columns -> limbs) are
+// in mont26.h, host and device, beside the cube they feed.
 
-__device__ __forceinline__ void pm_normalise(const PmShifts& K, const pm_v16i& Y, const uint64_t rk[5], uint32_t x[5]) {
-  const int32_t k0 = K.k0, k2 = K.k2, k4 = K.k4, k6 = K.k6, k16 = K.k16, k18 = K.k18, k20 = K.k20, k22 = K.k22;
-  auto mad = [](int32_t a, int32_t k, int64_t c) { return (int64_t)a * (int64_t)k + c; };
-  // two neighbouring digits of one limb first combine in 32 bits (|Y_c + 2^8 Y_c+1| < 2^30,
-  // one full-rate v_lshl_add_u32), so a limb takes one v_mad_i64_i32 per pair or lone digit:
-  // 10 quarter-rate mads per element instead of 16
-  auto pair = [](int32_t lo, int32_t hi) { return (int32_t)((uint32_t)lo + ((uint32_t)hi << 8)); };
-  // digit c sits at bit 8c = 26t + s
-  int64_t col[5];
-  col[0] = mad(pair(Y[2], Y[3]), k16, mad(pair(Y[0], Y[1]), k0, (int64_t)rk[0]));
-  col[1] = mad(Y[6], k22, mad(pair(Y[4], Y[5]), k6, (int64_t)rk[1]));
-  col[2] = mad(Y[9], k20, mad(pair(Y[7], Y[8]), k4, (int64_t)rk[2]));
-  col[3] = mad(Y[12], k18, mad(pair(Y[10], Y[11]), k2, (int64_t)rk[3]));
-  col[4] = mad(Y[15], k16, mad(pair(Y[13], Y[14]), k0, (int64_t)rk[4]));
-  uint32_t l[4];
-#pragma unroll
-  for (int t = 0; t < 4; t++) {
-    col[t + 1] += col[t] >> 26;
-    l[t] = (uint32_t)col[t] & M26;
-  }
-  // value = l0..l3 + (l4 + top 2^24) 2^104, 0 <= top < 2^16;
-  // top 2^128 == top (45 2^40 - 1) = top (2^26 - 1) + top 737279 2^26
-  const uint32_t top = (uint32_t)((uint64_t)col[4] >> 24);
-  const uint64_t a = (uint64_t)top * M26 + l[0];
-  const uint64_t b = (uint64_t)top * 737279u + (l[1] + (uint32_t)(a >> 26));
-  x[0] = (uint32_t)a & M26;
-  x[1] = (uint32_t)b & M26;
-  x[2] = l[2] + (uint32_t)(b >> 26);
-  x[3] = l[3];
-  x[4] = (uint32_t)col[4] & 0xFFFFFFu;
-}
-
-// cube of one element, written as its B fragment (16 offset bytes) and top bits
-__device__ __forceinline__ void pm_cube_pack(const uint32_t x[5], pm_v4i& b, uint32_t& top) {
-  uint32_t c[5];
-  mont_cube130(x, c);  // normalised limbs of a value < 2^129 (< 2^131 right after an absorb)
+// a cube's normalised limbs as its B fragment (16 offset bytes) and top bits (pm_pack_words)
+__device__ __forceinline__ void pm_pack(const uint32_t c[5], pm_v4i& b, uint32_t& top) {
   const uint32_t w0 = c[0] | (c[1] << 26);
   const uint32_t w1 = (c[1] >> 6) | (c[2] << 20);
   const uint32_t w2 = (c[2] >> 12) | (c[3] << 14);
@@ -268,13 +228,37 @@ __device__ __forceinline__ void pm_cube_pack(const uint32_t x[5], pm_v4i& b, uin
   b = pm_v4i{(int)(w0 ^ 0x80808080u), (int)(w1 ^ 0x80808080u), (int)(w2 ^ 0x80808080u), (int)(w3 ^ 0x80808080u)};
 }
 
+// cube of one element, written as its B fragment and top bits
+__device__ __forceinline__ void pm_cube_pack(const uint32_t x[5], pm_v4i& b, uint32_t& top) {
+  uint32_t c[5];
+  mont_cube130(x, c);  // normalised limbs of a value < 2^129 (< 2^131 right after an absorb)
+  pm_pack(c, b, top);
+}
+
+// The cubes of the round loop (the first cube of a permutation, right after an absorb, keeps the
+// form above): mont_cube130_chain gives the same limbs as mont_cube130 in fewer instructions, each
+// half of it one dependent chain.  pm_cube_finish is the second half and the packing; the caller
+// runs it beside the first half of the next element, so that two independent chains share the
+// VALU and neither waits on its own last result.
+__device__ __forceinline__ void pm_cube_finish(const uint32_t sq[5], const uint32_t x[5], pm_v4i& b, uint32_t& top) {
+  uint32_t c[5];
+  mont_mul130_chain(sq, x, c);  // normalised limbs of a value < 2^129
+  pm_pack(c, b, top);
+}
+__device__ __forceinline__ void pm_cube_pack_chain(const uint32_t x[5], pm_v4i& b, uint32_t& top) {
+  uint32_t sq[5];
+  mont_sq130_chain(x, sq);
+  pm_cube_finish(sq, x, b, top);
+}
+
 __device__ __forceinline__ pm_v4i pm_tops(const uint32_t t[6]) {
   return pm_v4i{(int)(t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24)), (int)(t[4] | (t[5] << 8)), 0, 0};
 }
 
 // One round on the cubes in b: the MFMAs of tile t are followed in program order by the
-// VALU work of element t-1 (normalise, then the next round's cube), so the wave's own
-// integer work runs while the matrix pipe finishes the later tiles.  The LDS operands are
+// VALU work of element t-1 (normalise, then the first half of the next round's cube) and of
+// element t-2 (the second half), so the wave's own integer work runs while the matrix pipe
+// finishes the later tiles.  The LDS operands are
 // software-pipelined: right after tile t's MFMAs are issued, the A fragments of tile t+1
 // (of tile 0 for the next round after the last tile) and the round-constant columns of
 // element t are requested, and a scheduling barrier keeps the requests ahead of element
@@ -296,6 +280,7 @@ __device__ __forceinline__ void pm_round(const PmShifts& K, const pm_v4i* af, co
   uint32_t tops[6];
   pm_v16i prev;
   uint64_t rkv[5];
+  uint32_t sq[5];  // the square of element t-1, multiplied out and packed one tile later
 #pragma unroll
   for (int t = 0; t < 6; t++) {
     pm_v16i acc = pm_v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -309,9 +294,12 @@ __device__ __forceinline__ void pm_round(const PmShifts& K, const pm_v4i* af, co
 #pragma unroll
     for (int l = 0; l < 5; l++) rkn[l] = rk[t * 10 + l];
     __builtin_amdgcn_sched_barrier(0);
+    // two independent chains per tile: element t-2's multiply and packing, element t-1's fold and
+    // square
+    if (NEXT && t > 1) pm_cube_finish(sq, x[t - 2], nb[t - 2], tops[t - 2]);
     if (t > 0) {
       pm_normalise(K, prev, rkv, x[t - 1]);
-      if (NEXT) pm_cube_pack(x[t - 1], nb[t - 1], tops[t - 1]);
+      if (NEXT) mont_sq130_chain(x[t - 1], sq);
     }
     prev = acc;
 #pragma unroll
@@ -319,9 +307,10 @@ __device__ __forceinline__ void pm_round(const PmShifts& K, const pm_v4i* af, co
 #pragma unroll
     for (int l = 0; l < 5; l++) rkv[l] = rkn[l];
   }
+  if (NEXT) pm_cube_finish(sq, x[4], nb[4], tops[4]);
   pm_normalise(K, prev, rkv, x[5]);
   if (NEXT) {
-    pm_cube_pack(x[5], nb[5], tops[5]);
+    pm_cube_pack_chain(x[5], nb[5], tops[5]);
     nb[6] = pm_tops(tops);
   }
 }
@@ -521,6 +510,11 @@ __device__ __forceinline__ pm_v4i pm16_tops(const uint32_t t[3]) {
 // One round on the cubes in b (k-steps 0..3): the four tiles of element group T, then the VALU
 // work of group T-1 (normalise, the next round's cube), the A fragments of the next tile
 // requested right after each tile's MFMAs, as pm_round.  rk: round constants of element g.
+// The chained cube runs whole here, unpaired: with three groups a round there is little to pair, and
+// with mont_cube130 beside the new pm_normalise these kernels need 153-168 VGPRs instead of
+// 100-115, a wave per SIMD less (profiles/r10/carry/summary.md).  These levels are bound by one
+// permutation's latency, which the serial chain lengthens: merkle_level_pm16_kernel 750 -> 826 us
+// per proof.
 template <bool NEXT>
 __device__ __forceinline__ void pm16_round(const PmShifts& K, const pm_v4i* af, const uint64_t* rk, const pm_v4i b[4],
                                            uint32_t x[3][5], pm_v4i nb[4], pm_v4i a[4]) {
@@ -547,7 +541,7 @@ __device__ __forceinline__ void pm16_round(const PmShifts& K, const pm_v4i* af, 
     __builtin_amdgcn_sched_barrier(0);
     if (T > 0) {
       pm_normalise(K, prev, rkv, x[T - 1]);
-      if (NEXT) pm_cube_pack(x[T - 1], nb[T - 1], tops[T - 1]);
+      if (NEXT) pm_cube_pack_chain(x[T - 1], nb[T - 1], tops[T - 1]);
     }
     prev = Y;
 #pragma unroll
@@ -555,7 +549,7 @@ __device__ __forceinline__ void pm16_round(const PmShifts& K, const pm_v4i* af, 
   }
   pm_normalise(K, prev, rkv, x[2]);
   if (NEXT) {
-    pm_cube_pack(x[2], nb[2], tops[2]);
+    pm_cube_pack_chain(x[2], nb[2], tops[2]);
     nb[3] = pm16_tops(tops);
   }
 }
