@@ -57,14 +57,8 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 // ------------------------------------------------------------------ quadratic extension (agg_air.h)
-void put(Bytes& b, fe x) { b.felem(x); }
-void put(Bytes& b, fe2 x) { b.felem(x.a); b.felem(x.b); }
 void flat(std::vector<fe>& v, fe x) { v.push_back(x); }
 void flat(std::vector<fe>& v, fe2 x) { v.push_back(x.a); v.push_back(x.b); }
-
-// RandomCoin::draw::<QuadExtension<f128>>: the 32 digest bytes as (a, b) (b = the digest's
-// zero upper half)
-fe2 draw_e2(Coin& c) { return E(c.draw()); }
 
 // ------------------------------------------------------------------ polynomials (small, host)
 // in-place radix-2 NTT in natural order over <w_m>; inverse includes 1/m
@@ -134,15 +128,11 @@ std::vector<fe> merkle(const std::vector<fe>& leaves) {
   for (size_t i = n; i-- > 1;) t[i] = hasher().merge(t[2 * i], t[2 * i + 1]);
   return t;
 }
-void multiproof(Bytes& b, const std::vector<fe>& tree, size_t n_leaves, const std::vector<size_t>& idx) {
-  const Plan plan = batch_plan(n_leaves, idx);
-  b.u8((uint8_t)ilog2(n_leaves));
-  b.u8((uint8_t)plan.len.size());
-  size_t k = 0;
-  for (uint32_t l : plan.len) {
-    b.u8((uint8_t)l);
-    for (uint32_t j = 0; j < l; j++) b.digest(tree[plan.node[k++]]);
-  }
+// the BatchMerkleProof of leaves idx of such a tree
+void multiproof(ProofWriter& w, const std::vector<fe>& tree, size_t n_leaves, const std::vector<size_t>& idx) {
+  Plan plan;
+  batch_plan_into(n_leaves, idx.data(), idx.size(), plan);
+  w.multiproof(plan, ilog2(n_leaves), [&](size_t i) { return tree[plan.node[i]]; });
 }
 
 // ------------------------------------------------------------------ public inputs (agg/pi.rs)
@@ -338,20 +328,6 @@ zkl_air_public_inputs replay_pi(const StepDecoded& s) {
 // AggColumns::baseline: the AggCol enum of agg_air.h
 constexpr size_t MIN_AGG_TRACE_ROWS = 8;
 
-// fold_positions_usize (agg/child.rs:1072-1100): pos mod (size / 2), deduplicated in order
-std::vector<size_t> fold_pos(const std::vector<size_t>& p, size_t size) {
-  std::vector<size_t> r;
-  for (size_t x : p) {
-    const size_t y = x % (size / 2);
-    if (std::find(r.begin(), r.end(), y) == r.end()) r.push_back(y);
-  }
-  return r;
-}
-size_t index_of(const std::vector<size_t>& v, size_t x) {
-  auto it = std::find(v.begin(), v.end(), x);
-  if (it == v.end()) throw AggError("FRI sample coset index not found in folded positions");
-  return (size_t)(it - v.begin());
-}
 // (x1 - x0) vnext == v1 (alpha - x0) - v0 (alpha - x1) at the coset of folded position y of a
 // layer of size `size` (constant domain offset, agg/trace.rs:759-821)
 fe fri_fold_at(fe v0, fe v1, fe alpha, size_t y, size_t size, fe* x0o = nullptr, fe* x1o = nullptr) {
@@ -362,11 +338,11 @@ fe fri_fold_at(fe v0, fe v1, fe alpha, size_t y, size_t size, fe* x0o = nullptr,
   const fe num = fe_sub(fe_mul(v1, fe_sub(alpha, x0)), fe_mul(v0, fe_sub(alpha, x1)));
   return fe_mul(num, fe_inv(fe_sub(x1, x0)));
 }
-// the value a layer of size `size` holds at position p (get_query_values geometry)
-fe layer_value(const SegmentView& v, int d, size_t p, size_t size) {
-  const size_t h = size / 2;
-  const size_t k = index_of(v.fri_positions[d], p % h);
-  return v.fri_values[d][2 * k + (p / h)];
+// the value layer d holds at the k-th position of the layer before it (of the query positions
+// for d = 0; get_query_values geometry)
+fe layer_value(const SegmentView& v, int d, size_t k) {
+  const size_t p = d ? v.fri_folds[d - 1].pos[k] : v.positions[k], h = (v.lde >> d) / 2;
+  return v.fri_values[d][2 * v.fri_folds[d].slot[k] + (p / h)];
 }
 
 // FS weights of the aggregation trace (agg/trace.rs:95-125)
@@ -417,11 +393,11 @@ std::vector<fe> fri_path_terms(const SegmentView& v, size_t s) {
   fe v_rem = fe_zero();
   size_t size = v.lde, pos_rem = 0;
   for (int d = 0; d < nl; d++) {
-    const auto& f = v.fri_positions[d];
+    const auto& f = v.fri_folds[d].pos;
     if (s >= f.size()) throw AggError("sample index out of bounds for FRI layer");
     const fe vn = fri_fold_at(v.fri_values[d][2 * s], v.fri_values[d][2 * s + 1], v.fri_alphas[d], f[s], size);
     if (d + 1 < nl) {
-      t.push_back(fe_sub(vn, layer_value(v, d + 1, f[s], size / 2)));
+      t.push_back(fe_sub(vn, layer_value(v, d + 1, s)));
     } else {
       v_rem = vn;
       pos_rem = f[s];
@@ -444,23 +420,23 @@ struct ChildTerms {
 };
 void child_terms(const SegmentView& v, ChildTerms& o) {
   try {
-    const size_t N = v.lde, y0 = v.fri_positions[0][0];
+    const size_t N = v.lde, y0 = v.fri_folds[0].pos[0];
     o.v0 = v.fri_values[0][0];
     o.v1 = v.fri_values[0][1];
     o.alpha = v.fri_alphas[0];
     o.vn = fri_fold_at(o.v0, o.v1, o.alpha, y0, N, &o.x0, &o.x1);
-    o.q1 = layer_value(v, 1, y0, N / 2);
+    o.q1 = layer_value(v, 1, 0);
     for (size_t k = 0; k < v.positions.size(); k++)
-      o.deep.push_back(fe_sub(deep_value(v, k), layer_value(v, 0, v.positions[k], v.lde)));
-    const auto& f0 = v.fri_positions[0];
+      o.deep.push_back(fe_sub(deep_value(v, k), layer_value(v, 0, k)));
+    const auto& f0 = v.fri_folds[0].pos;
     const size_t nk = std::min(f0.size(), v.positions.size());
     for (size_t k = 0; k < nk; k++) {
       const fe vn = fri_fold_at(v.fri_values[0][2 * k], v.fri_values[0][2 * k + 1], v.fri_alphas[0], f0[k], N);
-      o.layer1.push_back(fe_sub(vn, layer_value(v, 1, f0[k], N / 2)));
+      o.layer1.push_back(fe_sub(vn, layer_value(v, 1, k)));
     }
     o.path0 = fri_path_terms(v, 0);
     size_t paths = ~(size_t)0;
-    for (const auto& f : v.fri_positions) paths = std::min(paths, f.size());
+    for (const auto& f : v.fri_folds) paths = std::min(paths, f.pos.size());
     for (size_t k = 0; k < paths; k++) o.paths.push_back(k ? fri_path_terms(v, k) : o.path0);
   } catch (...) {
     o.err = std::current_exception();
@@ -624,7 +600,6 @@ struct AggOpts {
 template <class T>
 struct AggHostBackend final : AggBackend<T> {
   using AggBackend<T>::sh;
-  static void put_flat(std::vector<fe>& v, const T& x) { flat(v, x); }
   static constexpr fe off{3, 0};
 
   fe commit_trace(const std::vector<std::vector<fe>>& trace) override {
@@ -649,14 +624,8 @@ struct AggHostBackend final : AggBackend<T> {
   void compose(const std::vector<T>& alpha, const std::vector<T>& beta) override {
     const size_t W = sh.W, n = sh.n, N = sh.N, B = sh.B, ce = sh.ce;
     const auto& lde = this->lde;
-    // get_assertions (agg/air.rs:276-304) sorted by (step, column)
-    struct As { size_t col, step; fe v; };
-    const size_t last = n - 1;
-    const std::vector<As> asr = {{C_OK, 0, fe_zero()},
-                                 {C_V_UNITS_ACC, 0, fe_zero()},
-                                 {C_CHILD_COUNT_ACC, 0, fe_zero()},
-                                 {C_V_UNITS_ACC, last, sh.v_units_total},
-                                 {C_CHILD_COUNT_ACC, last, sh.children_count}};
+    AggAssertion asr[AGG_NA];
+    agg_assertions(n, sh.v_units_total, sh.children_count, asr);
     std::vector<T> cev(ce);
     const fe wce = root_of_unity((unsigned)ilog2(ce)), g = sh.g, gl = sh.gl;
     fe x = off;
@@ -674,8 +643,8 @@ struct AggHostBackend final : AggBackend<T> {
       T t = zero<T>();
       for (int k = 0; k < AGG_TC; k++) t = add(t, mulb(alpha[k], tc[k]));
       t = mulb(t, fe_mul(xg, fe_inv(fe_sub(xn, fe_one()))));
-      for (size_t a = 0; a < asr.size(); a++)
-        t = add(t, mulb(beta[a], fe_mul(fe_sub(cur[asr[a].col], asr[a].v), fe_inv(fe_sub(x, fe_pow64(g, asr[a].step))))));
+      for (int a = 0; a < AGG_NA; a++)
+        t = add(t, mulb(beta[a], fe_mul(fe_sub(cur[asr[a].col], asr[a].value), fe_inv(fe_sub(x, fe_pow64(g, asr[a].step))))));
       cev[i] = t;
     }
     this->cco = interpolate(cev, off);
@@ -692,7 +661,7 @@ struct AggHostBackend final : AggBackend<T> {
     std::vector<fe> cleaves(N), row;
     for (size_t i = 0; i < N; i++) {
       row.clear();
-      for (size_t j = 0; j < Cc; j++) put_flat(row, this->clde[j][i]);
+      for (size_t j = 0; j < Cc; j++) flat(row, this->clde[j][i]);
       cleaves[i] = H.hash_elements(row.data(), row.size());  // one partition: the whole row
     }
     this->ctree = merkle(cleaves);
@@ -727,8 +696,8 @@ struct AggHostBackend final : AggBackend<T> {
     std::vector<fe> lf(h), row;
     for (size_t i = 0; i < h; i++) {
       row.clear();
-      put_flat(row, ev[i]);
-      put_flat(row, ev[i + h]);
+      flat(row, ev[i]);
+      flat(row, ev[i + h]);
       lf[i] = H.hash_elements(row.data(), row.size());
     }
     this->ftrees.push_back(merkle(lf));
@@ -777,11 +746,8 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   o.batching_constraints = 0;
   o.batching_deep = 0;
   zkl_select_partitions((uint32_t)W, (uint32_t)n, &o.num_partitions, &o.hash_rate);
-  auto draw = [](Coin& c) -> T {
-    if constexpr (sizeof(T) == sizeof(fe2)) return draw_e2(c);
-    else return c.draw();
-  };
-  auto put_flat = [](std::vector<fe>& v, const T& x) { flat(v, x); };
+  // RandomCoin::draw::<E>: the 32 digest bytes as (a, b), b = the digest's zero upper half
+  auto draw = [](Coin& c) -> T { return lift<T>(c.draw()); };
 
   // AirContext: evaluation degrees, CE blowup, composition columns (winter-air [WF-recall])
   size_t max_eval = 0, ceb = 2;
@@ -815,11 +781,10 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
           throw AggError("aggregation trace does not satisfy ZlAggAir: transition constraint C" + std::to_string(k) +
                          " fails at row " + std::to_string(i));
     }
-    const size_t last = n - 1;
-    const bool ok = fe_is_zero(trace[C_OK][0]) && fe_is_zero(trace[C_V_UNITS_ACC][0]) &&
-                    fe_is_zero(trace[C_CHILD_COUNT_ACC][0]) && fe_eq(trace[C_V_UNITS_ACC][last], fe{v_units_total, 0}) &&
-                    fe_eq(trace[C_CHILD_COUNT_ACC][last], fe{children_count, 0});
-    if (!ok) throw AggError("aggregation trace does not satisfy ZlAggAir: an assertion fails");
+    AggAssertion asr[AGG_NA];
+    agg_assertions(n, fe{v_units_total, 0}, fe{children_count, 0}, asr);
+    for (const AggAssertion& a : asr)
+      if (!fe_eq(trace[a.col][a.step], a.value)) throw AggError("aggregation trace does not satisfy ZlAggAir: an assertion fails");
   }
   // select_partitions_for_trace gives one partition below 2^14 rows (a batch of <= 2^13
   // children); both backends hash a row whole
@@ -871,27 +836,25 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   };
   {
     std::vector<fe> oc;  // trace(z) | H(z) | trace(zg) | H(zg)  (agg/fs.rs:152-164)
-    for (auto& v : tz) put_flat(oc, as_T(v));
-    for (auto& v : hz) put_flat(oc, as_T(v));
-    for (auto& v : tzg) put_flat(oc, as_T(v));
-    for (auto& v : hzg) put_flat(oc, as_T(v));
+    for (auto& v : tz) flat(oc, as_T(v));
+    for (auto& v : hz) flat(oc, as_T(v));
+    for (auto& v : tzg) flat(oc, as_T(v));
+    for (auto& v : hzg) flat(oc, as_T(v));
     coin.reseed(H.hash_elements(oc.data(), oc.size()));
   }
   // 5. DEEP composition over the LDE domain
   std::vector<T> gam(W + Cc);
   for (auto& c : gam) c = draw(coin);
-  {
-    std::vector<T> frame;  // t(z) | t(zg) | H(z) | H(zg)
-    for (auto& v : tz) frame.push_back(as_T(v));
-    for (auto& v : tzg) frame.push_back(as_T(v));
-    for (auto& v : hz) frame.push_back(as_T(v));
-    for (auto& v : hzg) frame.push_back(as_T(v));
-    be.deep(as_T(z2), as_T(zg2), frame, gam);
-  }
+  std::vector<T> frame;  // t(z) | t(zg) | H(z) | H(zg)
+  for (auto& v : tz) frame.push_back(as_T(v));
+  for (auto& v : tzg) frame.push_back(as_T(v));
+  for (auto& v : hz) frame.push_back(as_T(v));
+  for (auto& v : hzg) frame.push_back(as_T(v));
+  be.deep(as_T(z2), as_T(zg2), frame, gam);
   // 6. FRI (folding 2, constant domain offset, remainder degree 1)
-  const size_t rem_max = (size_t)(o.fri_remainder_max_degree + 1) * B;
+  const int nl = fri_num_layers(N, B, o.fri_remainder_max_degree);
   std::vector<fe> fri_roots;
-  for (size_t Nd = N; Nd > rem_max; Nd /= 2) {
+  for (int d = 0; d < nl; d++) {
     fri_roots.push_back(be.fri_commit());
     coin.reseed(fri_roots.back());
     be.fri_fold(draw(coin));
@@ -903,7 +866,6 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   const std::vector<std::vector<T>>& layers = be.layers;
   const std::vector<std::vector<fe>>& ftrees = be.ftrees;
   const std::vector<T>& ev = be.ev;
-  const int nl = (int)layers.size();
   std::vector<T> rco = interpolate(ev, off);
   const size_t rlen = o.fri_remainder_max_degree + 1;
   for (size_t k = rlen; k < rco.size(); k++)
@@ -913,7 +875,7 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   fe rem_commit;
   {
     std::vector<fe> rf;
-    for (auto& v : rem) put_flat(rf, v);
+    for (auto& v : rem) flat(rf, v);
     rem_commit = H.hash_elements(rf.data(), rf.size());
   }
   coin.reseed(rem_commit);
@@ -950,67 +912,38 @@ std::vector<uint8_t> prove_air(const std::vector<std::vector<fe>>& trace, const 
   }
   if (grind_ms) *grind_ms = ms_since(t_grind);
   // 8. query positions: draw_integers(q, N, nonce), sort, dedup
-  coin.seed = H.merge_with_int(coin.seed, nonce);
-  coin.counter = 0;
   std::vector<size_t> pos;
-  for (uint32_t k = 0; k < ao.queries; k++) pos.push_back((size_t)(coin.draw().lo & (N - 1)));
-  std::sort(pos.begin(), pos.end());
-  pos.erase(std::unique(pos.begin(), pos.end()), pos.end());
+  query_positions(coin, nonce, ao.queries, N, pos);
   const size_t nq = pos.size();
 
-  // 9. Proof::to_bytes (the segment prover's layout; extension elements as two base elements)
+  // 9. Proof::to_bytes (proof_codec.h; an extension element is two base elements)
   Bytes P;
-  P.u8((uint8_t)W); P.u8(0); P.u8(0); P.u8((uint8_t)logn); P.u8(0); P.u8(0);
-  P.u8(16); P.felem(fe{P_LO, P_HI});
-  P.u8((uint8_t)o.num_queries); P.u8((uint8_t)o.blowup_factor); P.u8((uint8_t)o.grinding_factor);
-  P.u8((uint8_t)o.field_extension); P.u8((uint8_t)o.fri_folding_factor); P.u8((uint8_t)o.fri_remainder_max_degree);
-  P.u8((uint8_t)o.batching_constraints); P.u8((uint8_t)o.batching_deep);
-  P.u8((uint8_t)o.num_partitions); P.u8((uint8_t)o.hash_rate);
-  P.u8((uint8_t)nq);
-  {
-    Bytes cm;
-    cm.digest(ttree[1]); cm.digest(ctree[1]);
-    for (auto& r : fri_roots) cm.digest(r);
-    cm.digest(rem_commit);
-    P.vec(cm);
+  ProofWriter w{P};
+  w.context((uint32_t)W, logn, o, nq);
+  w.commitments(ttree[1], ctree[1], fri_roots, rem_commit);
+  std::vector<fe> tv;
+  std::vector<T> xv;  // a section's values of E
+  for (size_t k : pos) for (size_t c = 0; c < W; c++) tv.push_back(lde[c][k]);
+  for (size_t k : pos) for (size_t j = 0; j < Cc; j++) xv.push_back(clde[j][k]);
+  w.queries();
+  w.values(tv.data(), tv.size());
+  multiproof(w, ttree, N, pos);
+  w.values(xv.data(), xv.size());
+  multiproof(w, ctree, N, pos);
+  w.ood(frame.data(), frame.data() + W, W, frame.data() + 2 * W, frame.data() + 2 * W + Cc, Cc);
+  w.fri_layers(nl);
+  FoldStep f;
+  for (int d = 0; d < nl; d++) {
+    const size_t h = layers[d].size() / 2;
+    fold_positions(pos, h, f);
+    xv.clear();
+    for (size_t y : f.pos) { xv.push_back(layers[d][y]); xv.push_back(layers[d][y + h]); }
+    w.values(xv.data(), xv.size());
+    multiproof(w, ftrees[d], h, f.pos);
+    pos = f.pos;
   }
-  Bytes tv, tp, cv, cpb;
-  for (size_t k : pos) for (size_t c = 0; c < W; c++) tv.felem(lde[c][k]);
-  for (size_t k : pos) for (size_t j = 0; j < Cc; j++) put(cv, clde[j][k]);
-  multiproof(tp, ttree, N, pos);
-  multiproof(cpb, ctree, N, pos);
-  P.usize(1);
-  P.vec(tv); P.vec(tp);
-  P.vec(cv); P.vec(cpb);
-  {
-    Bytes ts, es;
-    for (auto& v : tz) put(ts, as_T(v));
-    for (auto& v : tzg) put(ts, as_T(v));
-    for (auto& v : hz) put(es, as_T(v));
-    for (auto& v : hzg) put(es, as_T(v));
-    P.vec(ts); P.vec(es);
-  }
-  P.usize((uint64_t)nl);
-  {
-    std::vector<size_t> p = pos;
-    for (int d = 0; d < nl; d++) {
-      const size_t Nd = layers[d].size(), h = Nd / 2;
-      std::vector<size_t> f;
-      for (size_t x : p) { const size_t y = x % h; if (std::find(f.begin(), f.end(), y) == f.end()) f.push_back(y); }
-      Bytes lv, lp;
-      for (size_t y : f) { put(lv, layers[d][y]); put(lv, layers[d][y + h]); }
-      multiproof(lp, ftrees[d], h, f);
-      P.vec(lv); P.vec(lp);
-      p = f;
-    }
-  }
-  {
-    Bytes rv;
-    for (auto& v : rem) put(rv, v);
-    P.vec(rv);
-  }
-  P.u8(0);  // FriProof num_partitions (log2 of 1)
-  P.u64(nonce);
+  w.remainder(rem.data(), rem.size());
+  w.finish(nonce);
   return P.v;
 }
 
@@ -1024,15 +957,6 @@ uint32_t conjectured_bits(uint32_t queries, uint32_t blowup, uint32_t grind, uin
   return std::min(std::min(field, qs) - 1, 128u);
 }
 
-template <class T> T read_e(Rd& r);
-template <> fe read_e<fe>(Rd& r) { return r.felem(); }
-template <> fe2 read_e<fe2>(Rd& r) { const fe a = r.felem(); return fe2{a, r.felem()}; }
-template <class T> T ext_of(fe2 v);
-template <> fe ext_of<fe>(fe2 v) { return v.a; }
-template <> fe2 ext_of<fe2>(fe2 v) { return v; }
-template <class T> T inv_t(T x);
-template <> fe inv_t<fe>(fe x) { return fe_inv(x); }
-template <> fe2 inv_t<fe2>(fe2 x) { return inv(x); }
 template <class T> bool eq_t(T x, T y);
 template <> bool eq_t<fe>(fe x, fe y) { return fe_eq(x, y); }
 template <> bool eq_t<fe2>(fe2 x, fe2 y) { return fe_eq(x.a, y.a) && fe_eq(x.b, y.b); }
@@ -1047,32 +971,25 @@ template <class T> T pow_t(T x, uint64_t e) {
 // prove.rs:732-791): transcript replay, out-of-domain identity through the same
 // agg_transition, trace / constraint openings, DEEP, FRI folds, remainder, proof of work
 template <class T>
-std::string verify_air(Rd& r, const AggPi& pi, const zkl_proof_options& o, uint32_t W, unsigned logn, size_t nq_proof) {
+std::string verify_air(Rd& r, const AggPi& pi, const ProofContext& cx) {
+  const zkl_proof_options& o = cx.opts;
+  const uint32_t W = cx.W, logn = cx.logn;
   const Hasher& H = hasher();
   const size_t n = (size_t)1 << logn, B = o.blowup_factor, N = n * B;
   size_t max_eval = 0;
   for (const Deg& d : kAggDegrees) max_eval = std::max(max_eval, (size_t)d.base * (n - 1) + (d.cycle ? n - 1 : 0));
   const size_t Cc = std::max<size_t>(1, (max_eval - (n - 1) + n - 1) / n);
-  const size_t rem_max = (size_t)(o.fri_remainder_max_degree + 1) * B;
-  int nl = 0;
-  for (size_t d = N; d > rem_max; d /= 2) nl++;
+  const int nl = fri_num_layers(N, B, o.fri_remainder_max_degree);
   fe troot, croot, rem_commit;
-  std::vector<fe> fri_roots(nl);
-  {
-    Rd cm = r.vec();
-    troot = cm.digest();
-    croot = cm.digest();
-    for (auto& x : fri_roots) x = cm.digest();
-    rem_commit = cm.digest();
-    if (!cm.done() || r.bad) return "malformed commitments";
-  }
+  std::vector<fe> fri_roots;
+  if (const char* e = read_commitments(r, nl, troot, croot, fri_roots, rem_commit)) return e;
   std::vector<fe> seed = context_elements(W, n, o);
   const std::vector<fe> pe = agg_pi_elements(pi);
   seed.insert(seed.end(), pe.begin(), pe.end());
   Coin coin{H.hash_elements(seed.data(), seed.size()), 0};
   auto draw = [&]() -> T { return lift<T>(coin.draw()); };  // draw::<E>: (value, 0)
   coin.reseed(troot);
-  std::vector<T> alpha(AGG_TC), beta(5);
+  std::vector<T> alpha(AGG_TC), beta(AGG_NA);
   for (auto& a : alpha) a = draw();
   for (auto& b : beta) b = draw();
   coin.reseed(croot);
@@ -1080,30 +997,29 @@ std::string verify_air(Rd& r, const AggPi& pi, const zkl_proof_options& o, uint3
   const fe g = root_of_unity(logn);
   const T zg = mul(z, lift<T>(g));
 
-  if (r.usize() != 1) return "trace queries: exactly one main segment expected";
-  Rd tq_v = r.vec(), tq_p = r.vec(), cq_v = r.vec(), cq_p = r.vec(), ood_ts = r.vec(), ood_es = r.vec();
-  if (r.bad) return "malformed query / OOD sections";
+  QuerySections qs;
+  if (const char* e = read_query_sections(r, qs)) return e;
+  Rd &tq_v = qs.tq_v, &tq_p = qs.tq_p, &cq_v = qs.cq_v, &cq_p = qs.cq_p, &ood_ts = qs.ood_ts, &ood_es = qs.ood_es;
   const size_t es = sizeof(T) / sizeof(fe) * 16;  // bytes per element of E
   if (ood_ts.len != 2 * W * es || ood_es.len != 2 * Cc * es) return "OOD frame has the wrong shape";
-  std::vector<T> tz(W), tzg(W), hz(Cc), hzg(Cc);
-  for (auto& v : tz) v = read_e<T>(ood_ts);
-  for (auto& v : tzg) v = read_e<T>(ood_ts);
-  for (auto& v : hz) v = read_e<T>(ood_es);
-  for (auto& v : hzg) v = read_e<T>(ood_es);
+  std::vector<T> tz, tzg, hz, hzg;
+  read_values(ood_ts, tz, W);
+  read_values(ood_ts, tzg, W);
+  read_values(ood_es, hz, Cc);
+  read_values(ood_es, hzg, Cc);
   if (ood_ts.bad || ood_es.bad) return "non-canonical OOD values";
   {  // H(z) = sum_j H_j(z) z^(j n) against the transition and boundary compositions at z
     const T zn = pow_t(z, n), gl = lift<T>(fe_pow64(g, n - 1));
-    const T p_last = mul(mul(gl, sub(zn, lift<T>(fe_one()))), inv_t(mul(lift<T>(fe{n, 0}), sub(z, gl))));
+    const T p_last = mul(mul(gl, sub(zn, lift<T>(fe_one()))), inv(mul(lift<T>(fe{n, 0}), sub(z, gl))));
     T tc[AGG_TC];
     agg_transition<T>(tz.data(), tzg.data(), p_last, tc);
     T t = zero<T>();
     for (int k = 0; k < AGG_TC; k++) t = add(t, mul(alpha[k], tc[k]));
-    t = mul(t, mul(sub(z, gl), inv_t(sub(zn, lift<T>(fe_one())))));
-    const size_t cols[5] = {C_OK, C_V_UNITS_ACC, C_CHILD_COUNT_ACC, C_V_UNITS_ACC, C_CHILD_COUNT_ACC};
-    const size_t steps[5] = {0, 0, 0, n - 1, n - 1};
-    const fe vals[5] = {fe_zero(), fe_zero(), fe_zero(), fe{pi.v_units_total, 0}, fe{pi.children_count, 0}};
-    for (int a = 0; a < 5; a++)
-      t = add(t, mul(beta[a], mul(sub(tz[cols[a]], lift<T>(vals[a])), inv_t(sub(z, lift<T>(fe_pow64(g, steps[a])))))));
+    t = mul(t, mul(sub(z, gl), inv(sub(zn, lift<T>(fe_one())))));
+    AggAssertion asr[AGG_NA];
+    agg_assertions(n, fe{pi.v_units_total, 0}, fe{pi.children_count, 0}, asr);
+    for (int a = 0; a < AGG_NA; a++)
+      t = add(t, mul(beta[a], mul(sub(tz[asr[a].col], lift<T>(asr[a].value)), inv(sub(z, lift<T>(fe_pow64(g, asr[a].step)))))));
     T h = zero<T>(), zj = lift<T>(fe_one());
     for (size_t j = 0; j < Cc; j++) { h = add(h, mul(hz[j], zj)); zj = mul(zj, zn); }
     if (!eq_t(h, t)) return "out-of-domain constraint identity does not hold";
@@ -1122,32 +1038,24 @@ std::string verify_air(Rd& r, const AggPi& pi, const zkl_proof_options& o, uint3
   for (int d = 0; d < nl; d++) { coin.reseed(fri_roots[d]); falpha[d] = draw(); }
   coin.reseed(rem_commit);
   // FRI layer sections, remainder, PoW nonce
-  if ((int)r.usize() != nl) return "FRI layer count mismatch";
-  std::vector<Rd> fl_v(nl), fl_p(nl);
-  for (int d = 0; d < nl; d++) { fl_v[d] = r.vec(); fl_p[d] = r.vec(); }
-  Rd remv = r.vec();
-  if (r.u8() != 0) return "FRI remainder partitions must be 1";
-  const uint64_t nonce = r.u64();
-  if (!r.done()) return "malformed FRI section or trailing bytes";
+  FriSections fs;
+  if (const char* e = read_fri_sections(r, nl, fs)) return e;
+  const uint64_t nonce = fs.nonce;
   {
     const fe d = H.merge_with_int(coin.seed, nonce);
     const uint32_t tzb = d.lo ? (uint32_t)__builtin_ctzll(d.lo) : 64u;
     if (tzb < o.grinding_factor) return "proof-of-work nonce does not meet the grinding factor";
   }
-  coin.seed = H.merge_with_int(coin.seed, nonce);
-  coin.counter = 0;
   std::vector<size_t> pos;
-  for (uint32_t k = 0; k < o.num_queries; k++) pos.push_back((size_t)(coin.draw().lo & (N - 1)));
-  std::sort(pos.begin(), pos.end());
-  pos.erase(std::unique(pos.begin(), pos.end()), pos.end());
+  query_positions(coin, nonce, o.num_queries, N, pos);
   const size_t nq = pos.size();
-  if (nq != nq_proof) return "num_unique_queries does not match the drawn positions";
+  if (nq != cx.nq) return "num_unique_queries does not match the drawn positions";
   // openings
   if (tq_v.len != nq * W * 16 || cq_v.len != nq * Cc * es) return "query value sections have the wrong size";
-  std::vector<fe> trows(nq * W);
-  std::vector<T> crows(nq * Cc);
-  for (auto& v : trows) v = tq_v.felem();
-  for (auto& v : crows) v = read_e<T>(cq_v);
+  std::vector<fe> trows;
+  std::vector<T> crows;
+  read_values(tq_v, trows, nq * W);
+  read_values(cq_v, crows, nq * Cc);
   if (tq_v.bad || cq_v.bad) return "non-canonical query values";
   {
     std::vector<fe> leaves(nq), row;
@@ -1168,7 +1076,7 @@ std::string verify_air(Rd& r, const AggPi& pi, const zkl_proof_options& o, uint3
   std::vector<T> ev(nq);
   for (size_t k = 0; k < nq; k++) {
     const T x = lift<T>(fe_mul(three, fe_pow64(wN, pos[k])));
-    const T iz = inv_t(sub(x, z)), izg = inv_t(sub(x, zg));
+    const T iz = inv(sub(x, z)), izg = inv(sub(x, zg));
     T y = zero<T>();
     for (size_t c = 0; c < W; c++) {
       const T t = lift<T>(trows[k * W + c]);
@@ -1183,33 +1091,33 @@ std::string verify_air(Rd& r, const AggPi& pi, const zkl_proof_options& o, uint3
   // FRI
   std::vector<size_t> fpos = pos;
   size_t Nd = N;
+  FoldStep fold;
+  std::vector<std::pair<size_t, uint32_t>> sorted;  // (folded position, its index in np)
+  std::vector<T> lv;
   for (int d = 0; d < nl; d++) {
     const size_t h = Nd / 2;
-    std::vector<size_t> np;
-    for (size_t p : fpos)
-      if (std::find(np.begin(), np.end(), p % h) == np.end()) np.push_back(p % h);
+    fold_positions(fpos, h, fold);
+    const std::vector<size_t>& np = fold.pos;
     const size_t m = np.size();
-    if (fl_v[d].len != 2 * m * es) return "FRI layer values have the wrong size";
-    std::vector<T> lv(2 * m);
-    for (auto& v : lv) v = read_e<T>(fl_v[d]);
-    if (fl_v[d].bad) return "non-canonical FRI layer values";
-    for (size_t k = 0; k < fpos.size(); k++) {
-      const size_t j = (size_t)(std::find(np.begin(), np.end(), fpos[k] % h) - np.begin());
-      if (!eq_t(lv[2 * j + (fpos[k] >= h ? 1 : 0)], ev[k])) return "FRI layer opening disagrees with the folded values";
-    }
+    if (fs.values[d].len != 2 * m * es) return "FRI layer values have the wrong size";
+    read_values(fs.values[d], lv, 2 * m);
+    if (fs.values[d].bad) return "non-canonical FRI layer values";
+    for (size_t k = 0; k < fpos.size(); k++)
+      if (!eq_t(lv[2 * fold.slot[k] + (fpos[k] >= h ? 1 : 0)], ev[k])) return "FRI layer opening disagrees with the folded values";
     {
-      std::vector<size_t> sp(np);
-      std::sort(sp.begin(), sp.end());
+      sorted_fold(np, sorted);
+      std::vector<size_t> sp(m);
       std::vector<fe> sl(m), row;
       for (size_t k = 0; k < m; k++) {
-        const size_t j = (size_t)(std::find(np.begin(), np.end(), sp[k]) - np.begin());
+        const size_t j = sorted[k].second;
+        sp[k] = sorted[k].first;
         row.clear();
         flat(row, lv[2 * j]);
         flat(row, lv[2 * j + 1]);
         sl[k] = H.hash_elements(row.data(), row.size());
       }
       fe root;
-      if (!batch_merkle_root(fl_p[d], h, sp, sl, &root) || !fe_eq(root, fri_roots[d]) || !fl_p[d].done())
+      if (!batch_merkle_root(fs.paths[d], h, sp, sl, &root) || !fe_eq(root, fri_roots[d]) || !fs.paths[d].done())
         return "FRI layer Merkle opening does not reproduce the layer commitment";
     }
     const fe gd = root_of_unity((unsigned)ilog2(Nd));
@@ -1224,10 +1132,10 @@ std::string verify_air(Rd& r, const AggPi& pi, const zkl_proof_options& o, uint3
     Nd = h;
   }
   const size_t rlen = o.fri_remainder_max_degree + 1;
-  if (remv.len != rlen * es) return "FRI remainder has the wrong size";
-  std::vector<T> rem(rlen);
-  for (auto& v : rem) v = read_e<T>(remv);
-  if (remv.bad) return "non-canonical remainder";
+  if (fs.remainder.len != rlen * es) return "FRI remainder has the wrong size";
+  std::vector<T> rem;
+  read_values(fs.remainder, rem, rlen);
+  if (fs.remainder.bad) return "non-canonical remainder";
   {
     std::vector<fe> rf;
     for (auto& v : rem) flat(rf, v);
@@ -1299,25 +1207,11 @@ std::string verify_artifact(const uint8_t* art, size_t len, uint32_t min_bits) {
   size_t plen;
   const AggPi pi = decode_artifact(art, len, &pb, &plen);
   Rd r{pb, plen, 0, false};
-  const uint32_t W = r.u8();
-  if (r.u8() != 0 || r.u8() != 0) return "trace info: auxiliary segments are not supported";
-  const unsigned logn = r.u8();
-  if (r.u8() != 0 || r.u8() != 0) return "trace info: trace metadata must be empty";
-  if (r.u8() != 16) return "context: field element size must be 16";
-  if (r.off + 16 > r.len) return "truncated context";
-  {
-    uint64_t m[2];
-    memcpy(m, r.p + r.off, 16);
-    if (m[0] != P_LO || m[1] != P_HI) return "field modulus in the context is not f128";
-    r.off += 16;
-  }
-  zkl_proof_options o{};
-  o.num_queries = r.u8(); o.blowup_factor = r.u8(); o.grinding_factor = r.u8();
-  o.field_extension = r.u8(); o.fri_folding_factor = r.u8(); o.fri_remainder_max_degree = r.u8();
-  o.batching_constraints = r.u8(); o.batching_deep = r.u8();
-  o.num_partitions = r.u8(); o.hash_rate = r.u8();
-  const size_t nq = r.u8();
-  if (r.bad) return "truncated context";
+  ProofContext cx;
+  if (const char* e = read_context(r, nullptr, cx)) return e;
+  const uint32_t W = cx.W;
+  const unsigned logn = cx.logn;
+  const zkl_proof_options& o = cx.opts;
   if (W != AGG_W) return "aggregation trace width must be 31 (AggColumns)";
   if (logn < 3 || logn > 13) return "aggregation trace length out of range";
   uint32_t np, rate;
@@ -1330,7 +1224,7 @@ std::string verify_artifact(const uint8_t* art, size_t len, uint32_t min_bits) {
   // AcceptableOptions::MinConjecturedSecurity(min_bits) (prove.rs:738)
   if (conjectured_bits(o.num_queries, o.blowup_factor, o.grinding_factor, o.field_extension) < min_bits)
     return "aggregation proof does not meet the requested conjectured security";
-  return o.field_extension == 2 ? verify_air<fe2>(r, pi, o, W, logn, nq) : verify_air<fe>(r, pi, o, W, logn, nq);
+  return o.field_extension == 2 ? verify_air<fe2>(r, pi, cx) : verify_air<fe>(r, pi, cx);
 }
 
 }  // namespace

@@ -117,5 +117,10 @@ __host__ __device__ inline void agg_transition(const RowC& c, const RowN& nx, T 
 __host__ __device__ inline int agg_assert_col(int a) {
   return a == 0 ? C_OK : (a == 1 || a == 3) ? C_V_UNITS_ACC : C_CHILD_COUNT_ACC;
 }
+struct AggAssertion { int col; size_t step; fe value; };
+inline void agg_assertions(size_t n, fe v_units_total, fe children_count, AggAssertion out[AGG_NA]) {
+  for (int a = 0; a < AGG_NA; a++)
+    out[a] = {agg_assert_col(a), a < 3 ? 0 : n - 1, a < 3 ? fe_zero() : a == 3 ? v_units_total : children_count};
+}
 
 }  // namespace zkl

@@ -1,7 +1,8 @@
-// Host pieces shared by the segment prover (prover.cpp) and the aggregation prover (agg.cpp):
-// the Fiat-Shamir coin, the winter-utils byte writer and the MerkleTree::prove_batch index
-// plan.  All three follow winterfell 0.13.1 [WF-recall]; the transcript order they serve is
-// pinned by agg/fs.rs:67-237.
+// Host pieces shared by the provers (prover.cpp, agg.cpp) and the verifiers (verifier.cpp,
+// agg.cpp): the Fiat-Shamir coin, the winter-utils byte writer and reader and the
+// MerkleTree::prove_batch index plan.  All follow winterfell 0.13.1 [WF-recall]; the transcript
+// order they serve is pinned by agg/fs.rs:67-237.  The layout of Proof::to_bytes over them is
+// proof_codec.h.
 #pragma once
 #include <string.h>
 
@@ -54,7 +55,61 @@ struct Bytes {
     const uint64_t w[4] = {x.lo, x.hi, 0, 0};
     raw(w, 32);
   }
-  void vec(const Bytes& b) { usize(b.v.size()); raw(b.v.data(), b.v.size()); }
+};
+
+// winter-utils ByteReader over a byte slice; `bad` latches on any overrun or non-canonical value
+struct Rd {
+  const uint8_t* p = nullptr;
+  size_t len = 0, off = 0;
+  bool bad = false;
+  uint8_t u8() {
+    if (off + 1 > len) { bad = true; return 0; }
+    return p[off++];
+  }
+  uint64_t u64() {
+    if (off + 8 > len) { bad = true; return 0; }
+    uint64_t v;
+    memcpy(&v, p + off, 8);
+    off += 8;
+    return v;
+  }
+  uint64_t usize() {  // vint64 (ByteReader::read_usize)
+    if (off >= len) { bad = true; return 0; }
+    const uint8_t b0 = p[off];
+    if (b0 == 0) { off++; return u64(); }
+    const int l = __builtin_ctz(b0) + 1;
+    if (off + (size_t)l > len) { bad = true; return 0; }
+    uint64_t enc = 0;
+    memcpy(&enc, p + off, (size_t)l);
+    off += (size_t)l;
+    return enc >> l;
+  }
+  fe felem() {  // 16-byte LE canonical element
+    if (off + 16 > len) { bad = true; return fe_zero(); }
+    fe v;
+    memcpy(&v.lo, p + off, 8);
+    memcpy(&v.hi, p + off + 8, 8);
+    off += 16;
+    if (v.hi > P_HI || (v.hi == P_HI && v.lo >= P_LO)) bad = true;
+    return v;
+  }
+  fe digest() {  // 32-byte digest: value + 16 zero bytes
+    const fe v = felem();
+    if (off + 16 > len) { bad = true; return v; }
+    for (int i = 0; i < 16; i++) bad |= p[off + (size_t)i] != 0;
+    off += 16;
+    return v;
+  }
+  Rd vec() {  // length-prefixed sub-slice
+    Rd s;
+    const uint64_t l = usize();
+    if (bad || off + l > len) { bad = true; s.bad = true; return s; }
+    s.p = p + off;
+    s.len = (size_t)l;
+    off += (size_t)l;
+    return s;
+  }
+  bool done() const { return !bad && off == len; }
 };
 
 // MerkleTree::prove_batch node-index plan: per normalized leaf pair, the tree-node indices
@@ -109,11 +164,6 @@ inline void batch_plan_into(size_t n_leaves, const size_t* idx, size_t Q, Plan& 
     o += cnt[k];
   }
   P.node.resize(o);
-}
-inline Plan batch_plan(size_t n_leaves, const std::vector<size_t>& idx) {
-  Plan P;
-  batch_plan_into(n_leaves, idx.data(), idx.size(), P);
-  return P;
 }
 
 }  // namespace zkl

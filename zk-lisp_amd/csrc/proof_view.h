@@ -14,22 +14,9 @@
 #include "../../include/zkl_hip.h"
 #include "air_host.h"
 #include "field.h"
+#include "proof_codec.h"
 
 namespace zkl {
-
-// winter-utils ByteReader over a byte slice; `bad` latches on any overrun or non-canonical value
-struct Rd {
-  const uint8_t* p = nullptr;
-  size_t len = 0, off = 0;
-  bool bad = false;
-  uint8_t u8();
-  uint64_t u64();
-  uint64_t usize();  // vint64 (ByteReader::read_usize)
-  fe felem();        // 16-byte LE canonical element
-  fe digest();       // 32-byte digest: value + 16 zero bytes
-  Rd vec();          // length-prefixed sub-slice
-  bool done() const { return !bad && off == len; }
-};
 
 // BatchMerkleProof::get_root (winter-crypto 0.13) for sorted unique leaf indices with their
 // digests; consumes the proof bytes from r.  Returns false if the proof is malformed.
@@ -113,7 +100,7 @@ struct SegmentView {
   // openings
   std::vector<fe> trace_rows;   // positions x W
   std::vector<fe> comp_rows;    // positions x C
-  std::vector<std::vector<size_t>> fri_positions;  // per layer: folded positions (order of first use)
+  std::vector<FoldStep> fri_folds;                 // per layer: folded positions and the slots folded into
   std::vector<std::vector<fe>> fri_values;         // per layer: [e_y, e_{y+h}] per folded position
   std::vector<fe> remainder;                       // reversed coefficients, degree <= rem_deg
   // the roots the trace / constraint openings reproduce when each opened row is hashed as the

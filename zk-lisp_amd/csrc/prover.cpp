@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "lde_plan.h"
 #include "host_proof.h"
+#include "proof_codec.h"
 #include "preflight.h"
 #include "tracegen_dev.h"
 #include "proof_view.h"
@@ -172,7 +173,7 @@ struct zkl_ctx {
   std::vector<uint8_t> proof_s;
   Plan tplan_s;                              // trace / constraint tree query plan
   std::vector<Plan> fplan_s;                 // FRI layer plans
-  std::vector<std::vector<size_t>> fpos_s;   // FRI layer query positions
+  std::vector<FoldStep> fpos_s;              // FRI layer query positions
   AirInstance air;
   // zkl_hip_trace_buffer: pinned host traces the caller fills in place (two slots: one filled
   // while the other's proof runs); zkl_hip_prove_segment DMAs columns straight from them
@@ -961,9 +962,7 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   T.mark(6);
 
   // ---- 6. FRI (FriProver::build_layers, folding 2, remainder degree rem_deg)
-  const size_t rem_max = (size_t)(o.fri_remainder_max_degree + 1) * B;
-  int nl = 0;
-  for (size_t d = N; d > rem_max; d /= 2) nl++;
+  const int nl = fri_num_layers(N, B, o.fri_remainder_max_degree);
   std::vector<size_t> ev_off(nl + 1), tr_off(nl);
   size_t ev_tot = 0, tr_tot = 0;
   for (int d = 0; d <= nl; d++) {
@@ -1088,9 +1087,7 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   HT("q_start");
   HT("q_drawn");
   std::vector<size_t> pos;
-  for (auto& v : qd) pos.push_back((size_t)(v.lo & (N - 1)));
-  std::sort(pos.begin(), pos.end());
-  pos.erase(std::unique(pos.begin(), pos.end()), pos.end());
+  query_positions(qd.data(), qd.size(), N, pos);
   const size_t nq = pos.size();
 
   HT("q_sorted");
@@ -1121,7 +1118,7 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   batch_plan_into(N, pos.data(), nq, tplan);
   append_nodes(C->tree.f(), tplan);
   append_nodes(C->ctree.f(), tplan);
-  std::vector<std::vector<size_t>>& fpos = C->fpos_s;
+  std::vector<FoldStep>& fpos = C->fpos_s;
   std::vector<Plan>& fplan = C->fplan_s;
   if (fpos.size() < (size_t)nl) fpos.resize(nl);
   if (fplan.size() < (size_t)nl) fplan.resize(nl);
@@ -1129,23 +1126,8 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
     size_t dsz = N;
     for (int d = 0; d < nl; d++) {
       const size_t h = dsz / 2;
-      const std::vector<size_t>& p = d ? fpos[d - 1] : pos;
-      std::vector<size_t>& f = fpos[d];
-      f.clear();
-      // fold positions, first occurrence kept (FriProver::build_proof order); a 512-slot open
-      // addressing set instead of a linear search per position (nq <= 256)
-      uint64_t seen_key[512];
-      uint8_t seen[512] = {0};
-      for (size_t x : p) {
-        const size_t y = x & (h - 1);
-        size_t k = (size_t)(((uint64_t)y * 0x9E3779B97F4A7C15ull) >> 55);
-        while (seen[k] && seen_key[k] != y) k = (k + 1) & 511;
-        if (!seen[k]) {
-          seen[k] = 1;
-          seen_key[k] = y;
-          f.push_back(y);
-        }
-      }
+      fold_positions(d ? fpos[d - 1].pos : pos, h, fpos[d]);
+      const std::vector<size_t>& f = fpos[d].pos;
       room(2 * f.size());
       for (size_t y : f) { *ap++ = (uint64_t)(uintptr_t)(layer_ev(d) + y); *ap++ = (uint64_t)(uintptr_t)(layer_ev(d) + y + h); }
       batch_plan_into(h, f.data(), f.size(), fplan[d]);
@@ -1176,76 +1158,29 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   P.v.swap(C->proof_s);
   P.v.clear();
   P.v.reserve(na_g * 32 + 4096);
-  P.u8((uint8_t)W); P.u8(0); P.u8(0); P.u8((uint8_t)logn); P.u8(0); P.u8(0);  // TraceInfo
-  P.u8(16); P.felem(fe{P_LO, P_HI});                                           // modulus bytes
-  P.u8((uint8_t)o.num_queries); P.u8((uint8_t)o.blowup_factor); P.u8((uint8_t)o.grinding_factor);
-  P.u8((uint8_t)o.field_extension); P.u8((uint8_t)o.fri_folding_factor); P.u8((uint8_t)o.fri_remainder_max_degree);
-  P.u8((uint8_t)o.batching_constraints); P.u8((uint8_t)o.batching_deep);
-  P.u8((uint8_t)o.num_partitions); P.u8((uint8_t)o.hash_rate);
-  P.u8((uint8_t)nq);
-  {
-    Bytes cm;
-    cm.digest(troot); cm.digest(croot);
-    for (auto& r : fri_roots) cm.digest(r);
-    cm.digest(rem_commit);
-    P.vec(cm);
-  }
-  // BatchMerkleProof bytes of a plan whose node values start at gv[g]: [depth][lists] then per
-  // list [len][len digests]; written with its vint length prefix (Vec<u8> of the proof)
-  auto mp_len = [](const Plan& plan) {
-    size_t n = 2 + plan.len.size();
-    for (uint32_t l : plan.len) n += 32 * (size_t)l;
-    return n;
-  };
-  auto emit_multiproof = [&](const Plan& plan, int depth, size_t g) {
-    const size_t len = mp_len(plan);
-    P.usize(len);
-    const size_t o = P.v.size();
-    P.v.resize(o + len);
-    uint8_t* w = P.v.data() + o;
-    *w++ = (uint8_t)depth;
-    *w++ = (uint8_t)plan.len.size();
-    for (uint32_t l : plan.len) {
-      *w++ = (uint8_t)l;
-      for (uint32_t k = 0; k < l; k++, w += 32) {  // digest: the 16 value bytes + 16 zero bytes
-        memcpy(w, gv + g++, 16);
-        memset(w + 16, 0, 16);
-      }
-    }
-  };
-  const size_t g_rows = 0, g_crows = nq * W, g_tnodes = nq * ((size_t)W + Cc), g_cnodes = g_tnodes + tplan.node.size();
-  P.usize(1);
-  P.usize(nq * W * sizeof(fe));  // felem = the 16 LE bytes of the canonical value
-  P.raw(gv + g_rows, nq * W * sizeof(fe));
-  emit_multiproof(tplan, logN, g_tnodes);
-  P.usize(nq * Cc * sizeof(fe));
-  P.raw(gv + g_crows, nq * Cc * sizeof(fe));
-  emit_multiproof(tplan, logN, g_cnodes);
+  ProofWriter wr{P};
+  wr.context(W, logn, o, nq);
+  wr.commitments(troot, croot, fri_roots, rem_commit);
+  // the gathered values in plan order: rows, constraint rows, the two trees' nodes, then per FRI
+  // layer its values and its nodes
+  auto gathered = [&](size_t g) { return [gv, g](size_t i) { return gv[g + i]; }; };
+  const size_t g_crows = nq * W, g_tnodes = nq * ((size_t)W + Cc), g_cnodes = g_tnodes + tplan.node.size();
+  wr.queries();
+  wr.values(gv, nq * W);
+  wr.multiproof(tplan, logN, gathered(g_tnodes));
+  wr.values(gv + g_crows, nq * Cc);
+  wr.multiproof(tplan, logN, gathered(g_cnodes));
   gi = g_cnodes + tplan.node.size();
-  {
-    Bytes ts, es;
-    for (auto& v : tz) ts.felem(v);
-    for (auto& v : tzg) ts.felem(v);
-    for (auto& v : hz) es.felem(v);
-    for (auto& v : hzg) es.felem(v);
-    P.vec(ts); P.vec(es);
-  }
-  P.usize((uint64_t)nl);
+  wr.ood(tz.data(), tzg.data(), W, hz.data(), hzg.data(), Cc);
+  wr.fri_layers(nl);
   for (int d = 0; d < nl; d++) {
-    const size_t nv = 2 * fpos[d].size();
-    P.usize(nv * sizeof(fe));
-    P.raw(gv + gi, nv * sizeof(fe));
-    gi += nv;
-    emit_multiproof(fplan[d], ilog2((N >> d) / 2), gi);
-    gi += fplan[d].node.size();
+    const size_t nv = 2 * fpos[d].pos.size();
+    wr.values(gv + gi, nv);
+    wr.multiproof(fplan[d], ilog2((N >> d) / 2), gathered(gi + nv));
+    gi += nv + fplan[d].node.size();
   }
-  {
-    Bytes rv;
-    for (auto& v : rem) rv.felem(v);
-    P.vec(rv);
-  }
-  P.u8(0);  // FriProof num_partitions (log2 of 1)
-  P.u64(nonce);
+  wr.remainder(rem.data(), rem.size());
+  wr.finish(nonce);
   if (gi != na_g) throw std::runtime_error("internal: gather plan mismatch");
   HT("serialised");
   T.finish();

@@ -31,54 +31,6 @@
 
 namespace zkl {
 
-uint8_t Rd::u8() {
-  if (off + 1 > len) { bad = true; return 0; }
-  return p[off++];
-}
-uint64_t Rd::u64() {
-  if (off + 8 > len) { bad = true; return 0; }
-  uint64_t v;
-  memcpy(&v, p + off, 8);
-  off += 8;
-  return v;
-}
-uint64_t Rd::usize() {
-  if (off >= len) { bad = true; return 0; }
-  const uint8_t b0 = p[off];
-  if (b0 == 0) { off++; return u64(); }
-  const int l = __builtin_ctz(b0) + 1;
-  if (off + (size_t)l > len) { bad = true; return 0; }
-  uint64_t enc = 0;
-  memcpy(&enc, p + off, (size_t)l);
-  off += (size_t)l;
-  return enc >> l;
-}
-fe Rd::felem() {
-  if (off + 16 > len) { bad = true; return fe_zero(); }
-  fe v;
-  memcpy(&v.lo, p + off, 8);
-  memcpy(&v.hi, p + off + 8, 8);
-  off += 16;
-  if (v.hi > P_HI || (v.hi == P_HI && v.lo >= P_LO)) bad = true;
-  return v;
-}
-fe Rd::digest() {
-  const fe v = felem();
-  if (off + 16 > len) { bad = true; return v; }
-  for (int i = 0; i < 16; i++) bad |= p[off + (size_t)i] != 0;
-  off += 16;
-  return v;
-}
-Rd Rd::vec() {
-  Rd s;
-  const uint64_t l = usize();
-  if (bad || off + l > len) { bad = true; s.bad = true; return s; }
-  s.p = p + off;
-  s.len = (size_t)l;
-  off += (size_t)l;
-  return s;
-}
-
 bool plan_batch_merkle(Rd& r, size_t n_leaves, const std::vector<size_t>& idx, const std::vector<uint32_t>& leaves,
                        HashPlan& plan, uint32_t* root) {
   // a rejected opening leaves the plan as it was: inputs and nodes are rolled back, merges are
@@ -92,8 +44,7 @@ bool plan_batch_merkle(Rd& r, size_t n_leaves, const std::vector<size_t>& idx, c
     plan.n_out = out0;
     return false;
   };
-  size_t depth = 0;
-  while (((size_t)1 << depth) < n_leaves) depth++;
+  const size_t depth = (size_t)ilog2(n_leaves);
   if (r.u8() != depth) return false;
   const size_t m = r.u8();
   std::vector<std::pair<uint32_t, size_t>> lists(m);  // first node, count
@@ -233,13 +184,6 @@ bool batch_merkle_root(Rd& r, size_t n_leaves, const std::vector<size_t>& idx, c
 
 namespace {
 
-struct VCoin {  // DefaultRandomCoin<PoseidonHasher> [WF-recall]
-  fe seed;
-  uint64_t counter = 0;
-  void reseed(fe d) { seed = hasher().merge(seed, d); counter = 0; }
-  fe draw() { return hasher().merge_with_int(seed, ++counter); }
-};
-
 size_t partition_size(uint32_t np, uint32_t rate, size_t ncols) {
   if (np <= 1) return ncols;
   const size_t a = (ncols + np - 1) / np;
@@ -282,8 +226,6 @@ void plan_reference_root(SegmentReplay& R, Rd proof, size_t N, const std::vector
 }
 
 constexpr uint32_t CHECK_OOD = PLAN_OUT - 1;
-
-int ilog2z(size_t n) { int k = 0; while (((size_t)1 << k) < n) k++; return k; }
 
 fe transition_sum(const AirInstance& air, const std::vector<fe>& cur, const std::vector<fe>& nxt, const fe* per,
                   fe p_last, const fe* alphas) {
@@ -328,28 +270,11 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
   Rd r{proof, len, 0, false};
 
   // ---- Context (TraceInfo, field modulus, ProofOptions) + num_unique_queries
-  const uint32_t W = r.u8();
-  if (r.u8() != 0 || r.u8() != 0) return "trace info: auxiliary segments are not supported";
-  const unsigned logn = r.u8();
-  if (r.u8() != 0 || r.u8() != 0) return "trace info: trace metadata must be empty";
-  if (r.u8() != 16) return "context: field element size must be 16";
-  if (r.off + 16 > r.len) return "truncated context";
-  {
-    uint64_t m[2];
-    memcpy(m, r.p + r.off, 16);
-    if (m[0] != P_LO || m[1] != P_HI) return "field modulus in the context is not f128";
-    r.off += 16;
-  }
-  zkl_proof_options po{};
-  po.num_queries = r.u8(); po.blowup_factor = r.u8(); po.grinding_factor = r.u8();
-  po.field_extension = r.u8(); po.fri_folding_factor = r.u8(); po.fri_remainder_max_degree = r.u8();
-  po.batching_constraints = r.u8(); po.batching_deep = r.u8();
-  po.num_partitions = r.u8(); po.hash_rate = r.u8();
-  if (want_opts && memcmp(&po, want_opts, sizeof po) != 0)
-    return "proof options in the proof differ from the expected options";
-  const zkl_proof_options opts = po;
-  const size_t nq_proof = r.u8();
-  if (r.bad) return "truncated context";
+  ProofContext cx;
+  if (const char* e = read_context(r, want_opts, cx)) return e;
+  const uint32_t W = cx.W;
+  const unsigned logn = cx.logn;
+  const zkl_proof_options& opts = cx.opts;
   {
     const std::string e = check_proof_options(opts);  // options decoded from the proof (winterfell reads them so)
     if (!e.empty()) return "proof options: " + e;
@@ -363,22 +288,12 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
     if (!e.empty()) return "AIR construction failed: " + e;
   }
   const int C = air.num_comp_cols;
-  const fe g = root_of_unity(logn), wN = root_of_unity(ilog2z(N));
-  const size_t rem_max = (size_t)(opts.fri_remainder_max_degree + 1) * opts.blowup_factor;
-  int nl = 0;
-  for (size_t d = N; d > rem_max; d /= 2) nl++;
+  const fe g = root_of_unity(logn), wN = root_of_unity(ilog2(N));
+  const int nl = fri_num_layers(N, opts.blowup_factor, opts.fri_remainder_max_degree);
   V.width = W; V.n = n; V.lde = N; V.comp_cols = C; V.opts = opts;
 
   // ---- Commitments
-  {
-    Rd cm = r.vec();
-    V.trace_root = cm.digest();
-    V.constraint_root = cm.digest();
-    V.fri_roots.resize(nl);
-    for (int d = 0; d < nl; d++) V.fri_roots[d] = cm.digest();
-    V.remainder_commit = cm.digest();
-    if (!cm.done() || r.bad) return "malformed commitments";
-  }
+  if (const char* e = read_commitments(r, nl, V.trace_root, V.constraint_root, V.fri_roots, V.remainder_commit)) return e;
 
   // ---- transcript up to the out-of-domain point
   std::vector<fe> seed = context_elements(W, n, opts);
@@ -386,7 +301,7 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
     const std::vector<fe> pe = pi_elements(pi);
     seed.insert(seed.end(), pe.begin(), pe.end());
   }
-  VCoin coin{H.hash_elements(seed.data(), seed.size()), 0};
+  Coin coin{H.hash_elements(seed.data(), seed.size()), 0};
   coin.reseed(V.trace_root);
   // composition coefficients: draw k = merge_with_int(seed, k), k = 1.. (alphas then betas).
   // They are independent, so the ~2.9e5 of a 2^16-row segment become one draw-range job of the
@@ -399,15 +314,14 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
   const fe z = V.z, zg = fe_mul(z, g);
 
   // ---- queries / OOD sections
-  if (r.usize() != 1) return "trace queries: exactly one main segment expected";
-  Rd tq_v = r.vec(), tq_p = r.vec(), cq_v = r.vec(), cq_p = r.vec(), ood_ts = r.vec(), ood_es = r.vec();
-  if (r.bad) return "malformed query / OOD sections";
+  QuerySections qs;
+  if (const char* e = read_query_sections(r, qs)) return e;
+  Rd &tq_v = qs.tq_v, &tq_p = qs.tq_p, &cq_v = qs.cq_v, &cq_p = qs.cq_p, &ood_ts = qs.ood_ts, &ood_es = qs.ood_es;
   if (ood_ts.len != 2 * (size_t)W * 16 || ood_es.len != 2 * (size_t)C * 16) return "OOD frame has the wrong shape";
-  V.ood_trace_z.resize(W); V.ood_trace_zg.resize(W); V.ood_comp_z.resize(C); V.ood_comp_zg.resize(C);
-  for (auto& v : V.ood_trace_z) v = ood_ts.felem();
-  for (auto& v : V.ood_trace_zg) v = ood_ts.felem();
-  for (auto& v : V.ood_comp_z) v = ood_es.felem();
-  for (auto& v : V.ood_comp_zg) v = ood_es.felem();
+  read_values(ood_ts, V.ood_trace_z, W);
+  read_values(ood_ts, V.ood_trace_zg, W);
+  read_values(ood_es, V.ood_comp_z, (size_t)C);
+  read_values(ood_es, V.ood_comp_zg, (size_t)C);
   if (ood_ts.bad || ood_es.bad) return "non-canonical OOD values";
 
   // ---- out-of-domain constraint identity: deferred to finish_replay, over the drawn coefficients
@@ -432,13 +346,9 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
   coin.reseed(V.remainder_commit);
 
   // ---- FRI proof sections, proof of work
-  if ((int)r.usize() != nl) return "FRI layer count mismatch";
-  std::vector<Rd> fl_v(nl), fl_p(nl);
-  for (int d = 0; d < nl; d++) { fl_v[d] = r.vec(); fl_p[d] = r.vec(); }
-  Rd remv = r.vec();
-  if (r.u8() != 0) return "FRI remainder partitions must be 1";
-  V.pow_nonce = r.u64();
-  if (!r.done()) return "malformed FRI section or trailing bytes";
+  FriSections fs;
+  if (const char* e = read_fri_sections(r, nl, fs)) return e;
+  V.pow_nonce = fs.nonce;
   {
     const fe h = H.merge_with_int(coin.seed, V.pow_nonce);
     const unsigned tz = h.lo ? (unsigned)__builtin_ctzll(h.lo) : 64u;
@@ -446,22 +356,15 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
   }
 
   // ---- query positions: draw_integers(q, N, nonce), sorted, de-duplicated
-  coin.seed = H.merge_with_int(coin.seed, V.pow_nonce);
-  coin.counter = 0;
-  V.positions.clear();
-  for (uint32_t k = 0; k < opts.num_queries; k++) V.positions.push_back((size_t)(coin.draw().lo & (N - 1)));
-  std::sort(V.positions.begin(), V.positions.end());
-  V.positions.erase(std::unique(V.positions.begin(), V.positions.end()), V.positions.end());
+  query_positions(coin, V.pow_nonce, opts.num_queries, N, V.positions);
   const std::vector<size_t>& pos = V.positions;
   const size_t nq = pos.size();
-  if (nq != nq_proof) return "num_unique_queries does not match the drawn positions";
+  if (nq != cx.nq) return "num_unique_queries does not match the drawn positions";
 
   // ---- trace and constraint openings
   if (tq_v.len != nq * W * 16 || cq_v.len != nq * (size_t)C * 16) return "query value sections have the wrong size";
-  V.trace_rows.resize(nq * W);
-  V.comp_rows.resize(nq * (size_t)C);
-  for (auto& v : V.trace_rows) v = tq_v.felem();
-  for (auto& v : V.comp_rows) v = cq_v.felem();
+  read_values(tq_v, V.trace_rows, nq * W);
+  read_values(cq_v, V.comp_rows, nq * (size_t)C);
   if (tq_v.bad || cq_v.bad) return "non-canonical query values";
   {
     uint32_t root;
@@ -509,63 +412,60 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
   }
 
   // ---- FRI: layer openings, folds, remainder
-  std::vector<size_t> fpos = pos;
   size_t Nd = N;
   const fe inv2 = fe_inv(fe{2, 0}), three{3, 0};
-  V.fri_positions.assign(nl, {});
+  V.fri_folds.assign(nl, {});
   V.fri_values.assign(nl, {});
+  std::vector<std::pair<size_t, uint32_t>> sorted;  // (folded position, its index in np)
   for (int d = 0; d < nl; d++) {
     const size_t h = Nd / 2;
-    std::vector<size_t>& np = V.fri_positions[d];
-    for (size_t p : fpos)
-      if (std::find(np.begin(), np.end(), p % h) == np.end()) np.push_back(p % h);
+    const std::vector<size_t>& fpos = d ? V.fri_folds[d - 1].pos : pos;
+    fold_positions(fpos, h, V.fri_folds[d]);
+    const std::vector<size_t>& np = V.fri_folds[d].pos;
+    const std::vector<uint32_t>& slot = V.fri_folds[d].slot;
     const size_t m = np.size();
-    if (fl_v[d].len != m * 32) return "FRI layer values have the wrong size";
+    if (fs.values[d].len != m * 32) return "FRI layer values have the wrong size";
     std::vector<fe>& lv = V.fri_values[d];
-    lv.resize(2 * m);
-    for (auto& v : lv) v = fl_v[d].felem();
-    if (fl_v[d].bad) return "non-canonical FRI layer values";
-    for (size_t k = 0; k < fpos.size(); k++) {
-      const size_t j = (size_t)(std::find(np.begin(), np.end(), fpos[k] % h) - np.begin());
-      if (!fe_eq(lv[2 * j + (fpos[k] >= h ? 1 : 0)], evals[k])) return "FRI layer opening disagrees with the folded values";
-    }
+    read_values(fs.values[d], lv, 2 * m);
+    if (fs.values[d].bad) return "non-canonical FRI layer values";
+    for (size_t k = 0; k < fpos.size(); k++)
+      if (!fe_eq(lv[2 * slot[k] + (fpos[k] >= h ? 1 : 0)], evals[k])) return "FRI layer opening disagrees with the folded values";
     {
-      std::vector<size_t> sp(np);
-      std::sort(sp.begin(), sp.end());
+      sorted_fold(np, sorted);
       const HashPlan::Mark mk = plan.mark();
       const uint32_t src = plan.add_in(lv.data(), lv.size());
+      std::vector<size_t> sp(m);
       std::vector<uint32_t> sl(m);  // leaf k: hash_elements of the value pair of sorted position k
       for (size_t k = 0; k < m; k++) {
-        const size_t j = (size_t)(std::find(np.begin(), np.end(), sp[k]) - np.begin());
+        sp[k] = sorted[k].first;
         sl[k] = plan.new_out();
-        plan.rows.push_back({src + (uint32_t)(2 * j), 2, 2, 0, sl[k]});
+        plan.rows.push_back({src + 2 * sorted[k].second, 2, 2, 0, sl[k]});
       }
       uint32_t root;
-      if (!plan_batch_merkle(fl_p[d], h, sp, sl, plan, &root) || !fl_p[d].done()) {
+      if (!plan_batch_merkle(fs.paths[d], h, sp, sl, plan, &root) || !fs.paths[d].done()) {
         plan.rewind(mk);
         return "FRI layer Merkle opening does not reproduce the layer commitment";
       }
       R.checks.push_back({root, V.fri_roots[d], "FRI layer Merkle opening does not reproduce the layer commitment"});
     }
     // fold: (v0 + v1)/2 + alpha (v0 - v1) / (2 x0), x0 = 3 w_Nd^y
-    const fe gd = root_of_unity(ilog2z(Nd));
+    const fe gd = root_of_unity(ilog2(Nd));
     std::vector<fe> next(m);
     for (size_t j = 0; j < m; j++) {
       const fe v0 = lv[2 * j], v1 = lv[2 * j + 1];
       const fe x0 = fe_mul(three, fe_pow64(gd, np[j]));
       next[j] = fe_mul(fe_add(fe_add(v0, v1), fe_mul(V.fri_alphas[d], fe_mul(fe_sub(v0, v1), fe_inv(x0)))), inv2);
     }
-    fpos = np;
     evals.swap(next);
     Nd = h;
   }
+  const std::vector<size_t>& fpos = nl ? V.fri_folds[nl - 1].pos : pos;
   const size_t rlen = opts.fri_remainder_max_degree + 1;
-  if (remv.len != rlen * 16) return "FRI remainder has the wrong size";
-  V.remainder.resize(rlen);
-  for (auto& v : V.remainder) v = remv.felem();
-  if (remv.bad) return "non-canonical remainder";
+  if (fs.remainder.len != rlen * 16) return "FRI remainder has the wrong size";
+  read_values(fs.remainder, V.remainder, rlen);
+  if (fs.remainder.bad) return "non-canonical remainder";
   if (!fe_eq(H.hash_elements(V.remainder.data(), rlen), V.remainder_commit)) return "remainder does not match its commitment";
-  const fe gr = root_of_unity(ilog2z(Nd));
+  const fe gr = root_of_unity(ilog2(Nd));
   for (size_t k = 0; k < fpos.size(); k++) {
     const fe x = fe_mul(three, fe_pow64(gr, fpos[k]));
     fe v = fe_zero(), xp = fe_one();
@@ -579,7 +479,7 @@ std::string replay_impl(const uint8_t* proof, size_t len, const zkl_air_public_i
 bool ood_identity_holds(const AirInstance& air, const SegmentView& V, const fe* alphas, const fe* betas) {
   const size_t n = V.n;
   const int C = V.comp_cols;
-  const fe z = V.z, g = root_of_unity((unsigned)ilog2z(n));
+  const fe z = V.z, g = root_of_unity((unsigned)ilog2(n));
   std::vector<fe> per = periodic_at(n, z);
   const fe gl = fe_pow64(g, n - 1), zn = fe_pow64(z, n);
   const fe p_last = fe_mul(fe_mul(gl, fe_sub(zn, fe_one())), fe_inv(fe_mul(fe{n, 0}, fe_sub(z, gl))));
