@@ -154,6 +154,39 @@ int zkl_hip_prove_segment(zkl_ctx* ctx, const zkl_f128* trace, uint32_t width, u
                           const zkl_air_public_inputs* pi, const zkl_proof_options* opts,
                           uint8_t** proof_out, size_t* proof_len);
 
+/* The same proof from the trace as a Winterfell TraceTable holds it: columns[c] is a host pointer
+ * to the n_rows elements of column c, or NULL for an all-zero column, so a binding passes
+ * trace.get_column(c).as_ptr() per column and builds no contiguous copy.  The caller must not
+ * write the columns during the call.  The request checks of zkl_hip_check_request that concern
+ * the shape (options, n_rows, width = the segment layout's width) run before any device work and
+ * before a column pointer is read; a NULL `columns` is ZKL_E_INVALID.  Same bytes as
+ * zkl_hip_prove_segment of the flattened trace; they stay available through zkl_hip_last_proof.
+ *
+ * Both host entry points stage the trace the same way (zkl_hip_prove_segment is this call with
+ * columns[c] = trace + c * n_rows): host threads classify every column while they read it (the
+ * rule of zkl_hip_scan_columns; a period that is not below n_rows counts as general), copy only
+ * the general columns into pinned memory and upload those, plus the first min(128, n_rows) rows
+ * of the periodic ones; the device then runs the structured trace LDE of a resident trace.  A
+ * trace inside a zkl_hip_trace_buffer is DMA'd in place instead and keeps the dense LDE. */
+int zkl_hip_prove_segment_columns(zkl_ctx* ctx, const zkl_f128* const* columns, uint32_t width, uint32_t n_rows,
+                                  const zkl_air_public_inputs* pi, const zkl_proof_options* opts,
+                                  uint8_t** proof_out, size_t* proof_len);
+/* What the last host-trace proof or zkl_hip_lde_columns_host call on ctx staged: the classes the
+ * host found, the trace bytes copied into pinned memory and the trace bytes DMA'd (both
+ * (general x n_rows + periodic x min(128, n_rows)) x 16 on the staged path), and the chunks of
+ * general columns issued.  A call that read nothing on the host (a pinned trace buffer, the
+ * preflight's whole upload) reports width general columns, width x n_rows x 16 bytes DMA'd and 0
+ * bytes pinned. */
+typedef struct {
+  uint32_t cols_zero, cols_periodic, cols_general, chunks;
+  uint64_t bytes_pinned, bytes_dma;
+} zkl_upload_stats;
+int zkl_hip_upload_stats(const zkl_ctx* ctx, zkl_upload_stats* out);
+/* General columns per staged chunk for the following host-trace calls on ctx: 0 (default) = what
+ * a pinned slot holds (slot bytes / column bytes), k > 0 = at most k, clamped so that a chunk
+ * fits a slot.  Results do not depend on it; small shapes use it to run the multi-chunk ring. */
+int zkl_hip_set_upload_chunk_columns(zkl_ctx* ctx, uint32_t k);
+
 /* Pinned host buffers owned by ctx for the next traces: slot 0 .. ZKL_TRACE_BUFFERS - 1, each at
  * least `bytes` (grown when needed, kept across proofs, freed by zkl_hip_destroy).  The caller
  * fills one -- zkl_build_segment_trace can write a segment straight into it -- and passes it as
@@ -401,6 +434,20 @@ int zkl_hip_hash_rows_periodic(zkl_ctx* ctx, const void* d_matrix, uint32_t n_co
  * next call or run that call with the switch off. */
 int zkl_hip_lde_columns(zkl_ctx* ctx, const void* d_values, uint32_t n_cols, uint32_t n_rows, uint32_t blowup,
                         const uint32_t* period, int want_split, void* d_coeffs_out, void* d_lde_out, int* split_out);
+
+/* The same stage from host columns (columns[c]: n_rows elements, or NULL for an all-zero column):
+ * the staging routine of zkl_hip_prove_segment_columns writing into caller device buffers.
+ * period_out[n_cols] (nullable) receives the classes the host found.  The book of what the
+ * context left zero in (d_coeffs_out, d_lde_out) is the one zkl_hip_lde_columns keeps, under the
+ * rules stated there. */
+int zkl_hip_lde_columns_host(zkl_ctx* ctx, const zkl_f128* const* columns, uint32_t n_cols, uint32_t n_rows,
+                             uint32_t blowup, int want_split, void* d_coeffs_out, void* d_lde_out,
+                             uint32_t* period_out, int* split_out);
+
+/* The classes the staging threads give host columns (host code, no ctx, no device): the encoding
+ * of zkl_hip_scan_columns, except that a period that is not below n_rows is ZKL_COL_GENERAL, as
+ * the LDE plan treats it.  Every row is compared; a NULL column is period 0. */
+int zkl_classify_columns(const zkl_f128* const* columns, uint32_t n_cols, uint32_t n_rows, uint32_t* period_out);
 
 /* Raw in-place radix-2 NTT on n_cols contiguous device columns of length n (stage test
  * entry point).  dif != 0: natural order in, bit-reversed out (Gentleman-Sande);

@@ -299,6 +299,16 @@ class ZkProver {
                   dev_->ctx());
     return Proof{detail::take(out, len)};
   }
+  // prove over column pointers, as winterfell's TraceTable holds its columns (one allocation each):
+  // columns[c] points to `length` elements, or is nullptr for an all-zero column; no contiguous
+  // copy is built (zkl_hip_prove_segment_columns)
+  Proof prove(const BaseElement* const* columns, uint32_t width, uint32_t length) const {
+    uint8_t* out = nullptr;
+    size_t len = 0;
+    detail::check(zkl_hip_prove_segment_columns(dev_->ctx(), columns, width, length, &pi_, &opts_.raw(), &out, &len),
+                  dev_->ctx());
+    return Proof{detail::take(out, len)};
+  }
   // same with the trace already resident in HBM (device pointer on this Device)
   Proof prove_device(const void* d_trace, uint32_t width, uint32_t length) const {
     uint8_t* out = nullptr;

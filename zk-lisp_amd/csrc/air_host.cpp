@@ -72,6 +72,17 @@ static void rom_weights(uint32_t seed, fe out[59]) {  // utils.rs:95-121
   for (int i = 0; i < 59; i++) { out[i] = cur; cur = fe_mul(cur, fe{3, 0}); }
 }
 
+// the layout's width for these public inputs against the trace's (the check build_air makes), on
+// its own: an entry point that reads `width` column pointers refuses a wrong width before it reads
+int trace_layout_width(const zkl_air_public_inputs& pi, uint32_t width) {
+  const uint64_t eff = pi.segment_feature_mask ? pi.segment_feature_mask : pi.feature_mask;
+  bool pid_nz = false;
+  for (int i = 0; i < 32; i++) pid_nz |= pi.program_id[i] != 0;
+  const Layout base = make_layout(true, true, true, true, true);
+  return ((int)width < base.width ? make_layout(eff & FM_VM, eff & FM_RAM, eff & FM_SPONGE, eff & FM_MERKLE, pid_nz)
+                                  : make_layout(true, true, true, true, pid_nz)).width;
+}
+
 // check_width false: the aggregation's child replay (agg/fs.rs:38-80), which rebuilds the AIR
 // with segment_feature_mask 0 as the reference does: ZkLispAir::new then takes the layout of the
 // program's mask for a narrow trace without comparing widths (vm/air/mod.rs:141-163); only the

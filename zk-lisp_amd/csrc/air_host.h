@@ -64,6 +64,10 @@ struct AirInstance {
 std::string build_air(const zkl_air_public_inputs& pi, uint32_t width, size_t n, AirInstance& out,
                       bool check_width = true);
 
+// The width build_air compares `width` with (the layout the feature mask implies), without
+// building the instance.
+int trace_layout_width(const zkl_air_public_inputs& pi, uint32_t width);
+
 // AirPublicInputs::to_elements (lib.rs:116-160)
 std::vector<fe> pi_elements(const zkl_air_public_inputs& pi);
 // Context::to_elements (winter-air 0.13.1, [WF-recall])

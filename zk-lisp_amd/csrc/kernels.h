@@ -214,15 +214,17 @@ void launch_intt_scaled(const fe* d_src, fe* d_data, size_t n_cols, size_t n, Mo
                         const fe* d_scale, hipStream_t s, const uint32_t* d_cmap = nullptr);
 int launch_lde_from_coeffs(const fe* d_coef, size_t n_cols, size_t n, size_t N, MontTab roots, size_t Ntab, fe* d_out,
                            hipStream_t s, bool want_split = false, const uint32_t* d_cmap = nullptr);
-// Periodic columns (period P, a power of two <= COL_P_MAX and below n) of the column-major n-row
-// matrix d_src, listed in d_cols: the B P-point coset LDE of each (B = N / n) goes to d_small[y *
-// small_stride ..] in natural row order, and the first min(COL_P_MAX, n) entries of its d_coef
-// column are written (the P scaled coefficients in the dense layout, zero after them; the caller
-// keeps the rest of the column zero).  d_roots / d_iroots: canonical tables w^i, w^-i of Ntab >= N
-// entries, d_opow: 3^k for k < n.
-void launch_periodic_lde(const fe* d_src, size_t n, size_t N, const uint32_t* d_cols, uint32_t n_cols, uint32_t P,
-                         const fe* d_roots, const fe* d_iroots, size_t Ntab, const fe* d_opow, fe* d_coef,
-                         fe* d_small, size_t small_stride, hipStream_t s);
+// Periodic columns (period P, a power of two <= COL_P_MAX and below n) listed in d_cols, their
+// first P rows read from d_src: at d_src + d_cols[y] * src_stride (a column-major matrix of row
+// stride src_stride; n for the n-row trace itself), or with src_packed at d_src + y * src_stride
+// (one block of rows per listed column).  d_src must not overlap d_coef.  The B P-point coset LDE
+// of each (B = N / n) goes to d_small[y * small_stride ..] in natural row order, and the first
+// min(COL_P_MAX, n) entries of its d_coef column are written (the P scaled coefficients in the
+// dense layout, zero after them; the caller keeps the rest of the column zero).  d_roots /
+// d_iroots: canonical tables w^i, w^-i of Ntab >= N entries, d_opow: 3^k for k < n.
+void launch_periodic_lde(const fe* d_src, size_t src_stride, bool src_packed, size_t n, size_t N, const uint32_t* d_cols,
+                         uint32_t n_cols, uint32_t P, const fe* d_roots, const fe* d_iroots, size_t Ntab,
+                         const fe* d_opow, fe* d_coef, fe* d_small, size_t small_stride, hipStream_t s);
 // LDE column d_cols[y] := its small LDE of d_bp[y] = B P rows repeated, in natural order or the
 // split layout (lde_pos below)
 void launch_periodic_tile(const fe* d_small, size_t small_stride, const uint32_t* d_cols, const uint32_t* d_bp,

@@ -969,15 +969,20 @@ void decode_column_scan(const uint32_t* bits, uint32_t ncols, size_t n, uint32_t
 // beyond P).  Both sums are split over min(256 / P, P) resp. min(4, P) threads per output and
 // added through LDS (field addition is exact, so the split does not show in the result): the
 // twiddle loads of a single 128-term chain per thread left the launch latency-bound.
+// The P source rows of column cols[y] are src[cols[y] * src_stride + t], or src[y * src_stride + t]
+// when src_packed is set (one row block per listed column, in list order).  src must not alias
+// coef: every block of a column reads its source rows while the chunk-0 block writes the column's
+// coef head.
 constexpr int PER_THREADS = 256, PER_EPARTS = 4, PER_ROWS = PER_THREADS / PER_EPARTS;
 __global__ __launch_bounds__(PER_THREADS) void periodic_lde_kernel(
-    const fe* __restrict__ src, size_t n, const uint32_t* __restrict__ cols, uint32_t logP, uint32_t logBP,
+    const fe* __restrict__ src, size_t src_stride, uint32_t src_packed, size_t n, const uint32_t* __restrict__ cols,
+    uint32_t logP, uint32_t logBP,
     const fe* __restrict__ roots, const fe* __restrict__ iroots, int logTab, const fe* __restrict__ opow, fe invP,
     uint32_t head, fe* __restrict__ coef, fe* __restrict__ small, size_t small_stride) {
   __shared__ fe v[COL_P_MAX], c[COL_P_MAX], red[PER_THREADS];
   const uint32_t P = 1u << logP, BP = 1u << logBP, t = threadIdx.x;
   const size_t col = cols[blockIdx.y];
-  if (t < P) v[t] = src[col * n + t];
+  if (t < P) v[t] = src[(src_packed ? (size_t)blockIdx.y : col) * src_stride + t];
   __syncthreads();
   {  // h_j = 1/P sum_i v_i w_P^(-i j): thread (part, j) sums the terms i of its part
     const uint32_t parts = min((uint32_t)PER_THREADS >> logP, P), len = P / parts;  // powers of two
@@ -1031,17 +1036,18 @@ __global__ __launch_bounds__(256) void periodic_tile_kernel(const fe* __restrict
     out[pos] = sm[lde_row(pos, N, split) & mask];
 }
 
-void launch_periodic_lde(const fe* d_src, size_t n, size_t N, const uint32_t* d_cols, uint32_t ncols, uint32_t P,
-                         const fe* d_roots, const fe* d_iroots, size_t Ntab, const fe* d_opow, fe* d_coef,
-                         fe* d_small, size_t small_stride, hipStream_t s) {
+void launch_periodic_lde(const fe* d_src, size_t src_stride, bool src_packed, size_t n, size_t N, const uint32_t* d_cols,
+                         uint32_t ncols, uint32_t P, const fe* d_roots, const fe* d_iroots, size_t Ntab,
+                         const fe* d_opow, fe* d_coef, fe* d_small, size_t small_stride, hipStream_t s) {
   if (ncols == 0) return;
   const size_t B = N / n;
-  if (P == 0 || (P & (P - 1)) || P > COL_P_MAX || P >= n || B * P > small_stride || B * P > Ntab || ncols > 65535)
+  if (P == 0 || (P & (P - 1)) || P > COL_P_MAX || P >= n || B * P > small_stride || B * P > Ntab || ncols > 65535 ||
+      src_stride < P)
     throw std::invalid_argument("launch_periodic_lde: period must be a power of two <= 128 and below n");
   const uint32_t BP = (uint32_t)(B * P), head = (uint32_t)std::min<size_t>(COL_P_MAX, n);
   static_assert(COL_P_MAX <= PER_THREADS, "one thread per coefficient of the head");
   periodic_lde_kernel<<<dim3((BP + PER_ROWS - 1) / PER_ROWS, ncols), PER_THREADS, 0, s>>>(
-      d_src, n, d_cols, (uint32_t)ilog2s(P), (uint32_t)ilog2s(BP), d_roots, d_iroots, ilog2s(Ntab), d_opow,
+      d_src, src_stride, src_packed ? 1u : 0u, n, d_cols, (uint32_t)ilog2s(P), (uint32_t)ilog2s(BP), d_roots, d_iroots, ilog2s(Ntab), d_opow,
       fe_inv(fe{P, 0}), head, d_coef, d_small, small_stride);
 }
 

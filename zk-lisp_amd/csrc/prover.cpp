@@ -11,6 +11,7 @@
 #include <atomic>
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
 #include <functional>
 #include <map>
 #include <memory>
@@ -25,6 +26,7 @@
 #include "../../include/zkl_hip.h"
 #include "agg_ctx.h"
 #include "air_host.h"
+#include "col_class.h"
 #include "host_hash.h"
 #include "kernels.h"
 #include "lde_plan.h"
@@ -48,6 +50,7 @@ namespace {
 #define HIPCHECK(x) ZKL_HIPCHECK(x)
 
 static_assert(LDE_COL_GENERAL == COL_GENERAL && LDE_P_MAX == COL_P_MAX, "lde_plan.h restates kernels.h");
+static_assert(CLASS_COL_GENERAL == COL_GENERAL && CLASS_P_MAX == COL_P_MAX, "col_class.h restates kernels.h");
 
 struct InvalidArg : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -158,6 +161,14 @@ struct zkl_ctx {
   std::vector<hipEvent_t> up_ev;
   size_t up_slot_bytes = 0;
   double up_ms = 0;  // host wall time of the last proof's upload loop
+  // the staged host trace (trace_lde_host_columns): the column map of the general columns, one
+  // slice per chunk, pinned and on the device; the first rows of the periodic columns, packed in
+  // the plan's order, pinned and on the device; general columns per chunk (0: what a slot holds);
+  // what the last host-trace call staged
+  HBuf h_cmap, h_phead;
+  DBuf cmap, phead;
+  uint32_t up_chunk_cols = 0;
+  zkl_upload_stats up_stats{};
   hipEvent_t stage_ev[ZKL_NUM_STAGES + 1] = {};
   bool stage_ev_ready = false;
   size_t pert_key_n = 0, pert_key_ce = 0;
@@ -395,10 +406,11 @@ void validate_request(uint32_t W, uint32_t n32, const zkl_air_public_inputs& pi,
 // Host-resident trace -> coefficient buffer, column chunk by column chunk, with the trace LDE of
 // each chunk (iNTT over <g>, coset shift, DIT evaluation, all per-column transforms) issued on
 // the compute stream as soon as its DMA lands.  The caller's trace is pageable memory (the Rust
-// binding passes its Vec): host threads copy each chunk into a pinned slot (ZKL_UP_SLOTS slots of
-// ZKL_UP_SLOT_MB), the copy stream DMAs the slot, the compute stream waits on that copy's event.
+// binding passes its columns): host threads stage each chunk in a pinned slot (UP_SLOTS slots of
+// UP_SLOT_BYTES), the copy stream DMAs the slot, the compute stream waits on that copy's event.
 // The PCIe upload thus overlaps the LDE of the chunks before it, and the host copy of chunk j+1
-// overlaps the DMA of chunk j.
+// overlaps the DMA of chunk j.  (trace_lde_host_columns below; upload_trace_direct is the form
+// with no host copy.)
 constexpr int UP_SLOTS = 4;
 constexpr size_t UP_SLOT_BYTES = (size_t)16 << 20;
 
@@ -420,72 +432,70 @@ static bool up_direct() {
   return d;
 }
 
-void parallel_copy(void* dst, const void* src, size_t bytes, unsigned nt) {
-  if (nt <= 1 || bytes < ((size_t)1 << 20)) { memcpy(dst, src, bytes); return; }
-  const size_t per = ((bytes + nt - 1) / nt + 63) & ~(size_t)63;
-  std::vector<std::thread> th;
-  for (unsigned t = 1; t < nt && t * per < bytes; t++)
-    th.emplace_back([=] { memcpy((char*)dst + t * per, (const char*)src + t * per, std::min(per, bytes - t * per)); });
-  memcpy(dst, src, std::min(per, bytes));
-  for (auto& x : th) x.join();
+void ensure_up_ring(zkl_ctx* C) {
+  if (C->up) return;
+  HIPCHECK(hipStreamCreateWithFlags(&C->up, hipStreamNonBlocking));
+  C->up_slot.assign(UP_SLOTS, nullptr);
+  C->up_ev.assign(UP_SLOTS, nullptr);
+  for (int k = 0; k < UP_SLOTS; k++) {
+    pin_alloc(&C->up_slot[k], UP_SLOT_BYTES);
+    HIPCHECK(hipEventCreateWithFlags(&C->up_ev[k], hipEventDisableTiming));
+  }
+  C->up_slot_bytes = UP_SLOT_BYTES;
 }
 
+double ms_since(std::chrono::steady_clock::time_point a) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+}
+
+// A host trace as the caller holds it: an array of column pointers (a null entry is an all-zero
+// column), or one block with column c at base + c * stride.
+struct ColSource {
+  const fe* const* cols = nullptr;
+  const fe* base = nullptr;
+  size_t stride = 0;
+  const fe* col(uint32_t c) const { return cols ? cols[c] : base + (size_t)c * stride; }
+};
+
+// a contiguous trace inside one of the context's own pinned buffers (zkl_hip_trace_buffer) is
+// DMA'd in place; ZKL_UP_MODE=direct does the same from pageable memory
+bool host_trace_in_tbuf(const zkl_ctx* C, const ColSource& src, uint32_t W, size_t n) {
+  if (!src.base || src.stride != n) return false;
+  bool in_tbuf = false;
+  for (const HBuf& b : C->tbuf)
+    in_tbuf |= b.p && (const char*)src.base >= (const char*)b.p &&
+               (const char*)src.base + (size_t)W * n * sizeof(fe) <= (const char*)b.p + b.bytes;
+  return in_tbuf;
+}
+bool host_trace_direct(const zkl_ctx* C, const ColSource& src, uint32_t W, size_t n) {
+  return src.base && src.stride == n && (up_direct() || host_trace_in_tbuf(C, src, W, n));
+}
+
+// The direct form: every chunk of a contiguous trace DMA'd from where it lies into coef, nothing
+// read on the host; on_chunk(c0, nc) queues the chunk's work on s behind its copy.
 template <class F>
-void upload_trace_chunked(zkl_ctx* C, const void* h_trace, uint32_t W, size_t n, hipStream_t s, F&& on_chunk) {
-  if (!C->up) {
-    HIPCHECK(hipStreamCreateWithFlags(&C->up, hipStreamNonBlocking));
-    C->up_slot.assign(UP_SLOTS, nullptr);
-    C->up_ev.assign(UP_SLOTS, nullptr);
-    for (int k = 0; k < UP_SLOTS; k++) {
-      pin_alloc(&C->up_slot[k], UP_SLOT_BYTES);
-      HIPCHECK(hipEventCreateWithFlags(&C->up_ev[k], hipEventDisableTiming));
-    }
-    C->up_slot_bytes = UP_SLOT_BYTES;
-  }
+void upload_trace_direct(zkl_ctx* C, const void* h_trace, uint32_t W, size_t n, hipStream_t s, F&& on_chunk) {
+  ensure_up_ring(C);
   const auto t0 = std::chrono::steady_clock::now();
   const size_t col_bytes = n * sizeof(fe);
   const uint32_t per = (uint32_t)std::max<size_t>(1, C->up_slot_bytes / col_bytes);
-  const unsigned nt = up_threads();
-  // a trace in one of the context's own pinned buffers (zkl_hip_trace_buffer) is DMA'd in place
-  bool in_tbuf = false;
-  for (const HBuf& b : C->tbuf)
-    in_tbuf |= b.p && (const char*)h_trace >= (const char*)b.p &&
-               (const char*)h_trace + (size_t)W * col_bytes <= (const char*)b.p + b.bytes;
-  const bool direct = in_tbuf || up_direct();
-  bool used[UP_SLOTS] = {false, false, false, false};
-  double copy_ms = 0, wait_ms = 0;
-  auto ms_since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
   int k = 0;
+  zkl_upload_stats st{};
   for (uint32_t c0 = 0; c0 < W; c0 += per, k = (k + 1) % UP_SLOTS) {
     const uint32_t nc = std::min(per, W - c0);
-    if (direct || col_bytes * nc > C->up_slot_bytes) {  // pageable copy (HIP stages it), or a column larger than a slot
-      HIPCHECK(hipMemcpyAsync(C->coef.f() + (size_t)c0 * n, (const char*)h_trace + c0 * col_bytes, col_bytes * nc,
-                              hipMemcpyHostToDevice, direct ? C->up : s));
-      if (direct) {
-        HIPCHECK(hipEventRecord(C->up_ev[k], C->up));
-        HIPCHECK(hipStreamWaitEvent(s, C->up_ev[k], 0));
-      }
-      on_chunk(c0, nc);
-      continue;
-    }
-    auto tw = std::chrono::steady_clock::now();
-    if (used[k]) HIPCHECK(hipEventSynchronize(C->up_ev[k]));  // the slot's previous DMA has read it
-    wait_ms += ms_since(tw);
-    auto tc = std::chrono::steady_clock::now();
-    parallel_copy(C->up_slot[k], (const char*)h_trace + c0 * col_bytes, col_bytes * nc, nt);
-    copy_ms += ms_since(tc);
-    HIPCHECK(hipMemcpyAsync(C->coef.f() + (size_t)c0 * n, C->up_slot[k], col_bytes * nc, hipMemcpyHostToDevice, C->up));
+    HIPCHECK(hipMemcpyAsync(C->coef.f() + (size_t)c0 * n, (const char*)h_trace + c0 * col_bytes, col_bytes * nc,
+                            hipMemcpyHostToDevice, C->up));
     HIPCHECK(hipEventRecord(C->up_ev[k], C->up));
-    used[k] = true;
     HIPCHECK(hipStreamWaitEvent(s, C->up_ev[k], 0));
     on_chunk(c0, nc);
+    st.chunks++;
   }
+  st.cols_general = W;  // nothing was classified on the host
+  st.bytes_dma = (uint64_t)W * col_bytes;
+  C->up_stats = st;
   C->up_ms = ms_since(t0);
   if (getenv("ZKL_UP_DEBUG"))
-    fprintf(stderr, "[zkl upload] %u cols x %zu rows: loop %.2f ms (host copy %.2f ms on %u threads, slot waits %.2f ms)%s\n",
-            W, n, C->up_ms, copy_ms, nt, wait_ms, in_tbuf ? " pinned trace buffer" : direct ? " direct" : "");
+    fprintf(stderr, "[zkl upload] %u cols x %zu rows: loop %.2f ms, direct\n", W, n, C->up_ms);
 }
 
 // proofs running in any context: the row-digest rule (a process-wide test switch, DESIGN.md
@@ -569,7 +579,7 @@ int trace_lde_columns(zkl_ctx* C, ZeroBook& book, const fe* d_src, uint32_t W, s
       for (uint32_t a = 0; a < npc;) {  // one small-LDE launch per period present
         uint32_t b = a;
         while (b < npc && pl.pper[b] == pl.pper[a]) b++;
-        launch_periodic_lde(d_src, n, N, m.pcols + a, b - a, pl.pper[a], C->roots.f(), C->iroots.f(), Ntab,
+        launch_periodic_lde(d_src, n, false, n, N, m.pcols + a, b - a, pl.pper[a], C->roots.f(), C->iroots.f(), Ntab,
                             C->opow.f(), coef, C->psmall.f() + (size_t)a * stride, stride, s);
         a = b;
       }
@@ -580,9 +590,232 @@ int trace_lde_columns(zkl_ctx* C, ZeroBook& book, const fe* d_src, uint32_t W, s
   return split;
 }
 
+// The trace LDE of a host trace (the same result as trace_lde_columns on the uploaded matrix),
+// shared by prove_impl and zkl_hip_lde_columns_host.  The host threads that stage the trace read
+// every byte of it anyway, so they classify each column as they go (classify_column, the device
+// scan's rule) and only what the device needs crosses the bus: the general columns, staged chunk
+// by chunk through the pinned ring and DMA'd each into its own coef column, and the first
+// R = min(COL_P_MAX, n) rows of the periodic ones.  A zero column is neither staged nor uploaded.
+//
+// Workers (up_threads(), started once per call; none for a trace under 256 KiB) take the columns in
+// order: classify, then commit in column order, which gives a general column its ordinal g, hence
+// its chunk g / per and its place in that chunk's slot, then copy.  A slot is written only once the
+// DMA of the chunk that used it before has read it.  The calling thread issues each chunk as soon
+// as its columns are staged: the DMAs and the chunk's slice of the column map on the copy stream,
+// then, behind that copy's event, the chunk's iNTT and LDE passes in place through the map.  The
+// map words of a call live in one pinned and one device buffer of W words; each chunk writes and
+// uploads only its own slice (h_meta, written once per call by upload_col_meta, is not used here).
+// After the last chunk every class is known: the plan against the book, the clears it lists, the
+// column lists, and the periodic columns from their packed first rows (a scratch of row stride R:
+// the periodic kernel's source must not alias coef, which here is the upload target).
+//
+// colstruct off: every column is general, staged and transformed (a null column as zeros).
+// Columns longer than a slot go straight from the caller's memory, general ones only.  period
+// receives the W classes; *meta_out the device lists (left alone with colstruct off).  Returns the
+// layout of every LDE column (1 = split).
+int trace_lde_host_columns(zkl_ctx* C, ZeroBook& book, const ColSource& src, uint32_t W, size_t n, size_t N,
+                           bool colstruct, fe* coef, fe* lde, bool want_split, uint32_t* period, ColMeta* meta_out,
+                           hipStream_t s) {
+  ensure_up_ring(C);
+  const auto t0 = std::chrono::steady_clock::now();
+  const MontTab mi = mont_tab(C->miroots.p, C->tab_N), mr = mont_tab(C->mroots.p, C->tab_N);
+  const size_t Ntab = C->tab_N;
+  const size_t col_bytes = n * sizeof(fe), R = std::min<size_t>(COL_P_MAX, n);
+  const uint32_t B = (uint32_t)(N / n);
+  const bool big = col_bytes > C->up_slot_bytes;
+  uint32_t per = big ? 1 : (uint32_t)(C->up_slot_bytes / col_bytes);
+  if (C->up_chunk_cols) per = std::min(per, C->up_chunk_cols);
+  C->h_cmap.ensure((size_t)W * sizeof(uint32_t));
+  C->cmap.ensure((size_t)W * sizeof(uint32_t));
+  uint32_t* hmap = C->h_cmap.at<uint32_t>();  // the last call that read it has synchronised
+  const uint32_t* dmap = (const uint32_t*)C->cmap.p;
+  book.begin(coef, lde, n, N, W);
+  zkl_upload_stats st{};
+  int split = -1;
+  double wait_ms = 0;
+
+  auto slot_at = [&](uint32_t g) { return (char*)C->up_slot[(g / per) % UP_SLOTS] + (size_t)(g % per) * col_bytes; };
+  auto stage = [&](uint32_t c, uint32_t g) {  // general column c, ordinal g, into its slot
+    if (big) return;
+    if (const fe* p = src.col(c)) memcpy(slot_at(g), p, col_bytes);
+    else memset(slot_at(g), 0, col_bytes);
+  };
+  // chunk j = general ordinals [j per, j per + cnt): copies (runs of adjacent columns as one), its
+  // map slice, and its transforms behind them
+  auto issue = [&](uint32_t j, uint32_t cnt) {
+    const uint32_t g0 = j * per, k = j % UP_SLOTS;
+    hipStream_t cs = big ? s : C->up;
+    for (uint32_t a = 0; a < cnt;) {
+      uint32_t b = a + 1;
+      while (!big && b < cnt && hmap[g0 + b] == hmap[g0 + b - 1] + 1) b++;
+      fe* dst = coef + (size_t)hmap[g0 + a] * n;
+      const void* from = big ? (const void*)src.col(hmap[g0 + a]) : (const void*)slot_at(g0 + a);
+      if (from) HIPCHECK(hipMemcpyAsync(dst, from, (size_t)(b - a) * col_bytes, hipMemcpyHostToDevice, cs));
+      else HIPCHECK(hipMemsetAsync(dst, 0, col_bytes, cs));
+      a = b;
+    }
+    HIPCHECK(hipMemcpyAsync((void*)(dmap + g0), hmap + g0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
+    if (!big) {
+      HIPCHECK(hipEventRecord(C->up_ev[k], C->up));
+      HIPCHECK(hipStreamWaitEvent(s, C->up_ev[k], 0));
+    }
+    launch_intt_scaled(nullptr, coef, cnt, n, mi, Ntab, C->opow_n.f(), s, dmap + g0);
+    const int sp = launch_lde_from_coeffs(coef, cnt, n, N, mr, Ntab, lde, s, want_split, dmap + g0);
+    // the row hash, evaluator and DEEP read every column with one layout (the NTT mode cannot
+    // change during a proof: zkl_hip_set_ntt_mode refuses while one is in flight)
+    if (split >= 0 && sp != split) throw std::runtime_error("internal: trace LDE chunks in different layouts");
+    split = sp;
+    st.chunks++;
+  };
+  auto wait_slot_of = [&](uint32_t j) {  // the DMA of chunk j has read its slot
+    const auto tw = std::chrono::steady_clock::now();
+    HIPCHECK(hipEventSynchronize(C->up_ev[j % UP_SLOTS]));
+    wait_ms += ms_since(tw);
+  };
+
+  const unsigned nt = (size_t)W * col_bytes < ((size_t)256 << 10) ? 1 : up_threads();
+  uint32_t ng = 0;
+  if (nt <= 1) {
+    for (uint32_t c = 0; c < W; c++) {
+      const uint32_t P = colstruct ? classify_column(src.col(c), n) : COL_GENERAL;
+      period[c] = P;
+      if (P != COL_GENERAL) continue;
+      const uint32_t j = ng / per;
+      if (!big && ng % per == 0 && j >= (uint32_t)UP_SLOTS) wait_slot_of(j);
+      stage(c, ng);
+      hmap[ng++] = c;
+      if (ng % per == 0) issue(j, per);
+    }
+    if (ng % per) issue(ng / per, ng % per);
+  } else {
+    struct {
+      std::mutex m;
+      std::condition_variable cv;
+      uint32_t next_commit = 0, ng = 0;
+      uint32_t allowed = UP_SLOTS - 1;  // the highest chunk whose slot may be written
+      std::vector<uint32_t> staged;     // per chunk: columns staged so far
+      bool failed = false;
+    } sh;
+    sh.staged.assign(W / per + 2, 0);
+    std::atomic<uint32_t> next_col{0};
+    auto worker = [&] {
+      for (;;) {
+        const uint32_t c = next_col.fetch_add(1);
+        if (c >= W) return;
+        const uint32_t P = colstruct ? classify_column(src.col(c), n) : COL_GENERAL;
+        uint32_t g = 0;
+        {
+          std::unique_lock<std::mutex> lk(sh.m);
+          sh.cv.wait(lk, [&] { return sh.next_commit == c || sh.failed; });
+          if (sh.failed) return;
+          period[c] = P;
+          if (P == COL_GENERAL) hmap[g = sh.ng++] = c;
+          sh.next_commit = c + 1;
+          sh.cv.notify_all();
+          if (P != COL_GENERAL) continue;
+          sh.cv.wait(lk, [&] { return big || sh.allowed >= g / per || sh.failed; });
+          if (sh.failed) return;
+        }
+        stage(c, g);
+        std::lock_guard<std::mutex> lk(sh.m);
+        sh.staged[g / per]++;
+        sh.cv.notify_all();
+      }
+    };
+    std::vector<std::thread> th;
+    struct Join {  // an error on the issuing thread releases and collects the workers first
+      decltype(sh)& sh;
+      std::vector<std::thread>& th;
+      ~Join() {
+        {
+          std::lock_guard<std::mutex> lk(sh.m);
+          sh.failed = true;
+        }
+        sh.cv.notify_all();
+        for (auto& t : th) t.join();
+      }
+    } join{sh, th};
+    for (unsigned t = 0; t < nt; t++) th.emplace_back(worker);
+    for (uint32_t j = 0;; j++) {
+      uint32_t cnt = 0;
+      {
+        std::unique_lock<std::mutex> lk(sh.m);
+        sh.cv.wait(lk, [&] {
+          if (sh.staged[j] == per) return true;
+          return sh.next_commit == W && sh.staged[j] == std::min(per, sh.ng - std::min(sh.ng, j * per));
+        });
+        cnt = sh.staged[j];
+      }
+      if (cnt == 0) break;
+      issue(j, cnt);
+      if (cnt < per) break;
+      // the slots of chunks up to j + UP_SLOTS - 1 are free once the DMA of chunk j - 1 is done
+      if (!big && j >= 1) wait_slot_of(j - 1);
+      {
+        std::lock_guard<std::mutex> lk(sh.m);
+        sh.allowed = j + UP_SLOTS - 1;
+      }
+      sh.cv.notify_all();
+    }
+    ng = sh.ng;
+  }
+  // with no general column this still reports the layout the later readers expect
+  if (split < 0) split = launch_lde_from_coeffs(coef, 0, n, N, mr, Ntab, lde, s, want_split, dmap);
+
+  uint32_t npc = 0;
+  if (!colstruct) {
+    book.all_unknown();  // the upload wrote every coef column
+  } else {
+    const LdePlan pl = plan_structured_lde(period, W, n, book);
+    if (pl.general.size() != ng || !std::equal(pl.general.begin(), pl.general.end(), hmap))
+      throw std::logic_error("internal: staged columns differ from the plan's general columns");
+    const ColMeta m = upload_col_meta(C, pl, W, B, s);
+    if (meta_out) *meta_out = m;
+    for (auto& r : pl.clear_all) {
+      HIPCHECK(hipMemsetAsync(coef + (size_t)r.first * n, 0, (size_t)(r.second - r.first) * n * sizeof(fe), s));
+      HIPCHECK(hipMemsetAsync(lde + (size_t)r.first * N, 0, (size_t)(r.second - r.first) * N * sizeof(fe), s));
+    }
+    for (auto& r : pl.clear_tail)
+      for (uint32_t c = r.first; c < r.second; c++)  // the heads in between are written below
+        HIPCHECK(hipMemsetAsync(coef + (size_t)c * n + R, 0, (n - R) * sizeof(fe), s));
+    npc = (uint32_t)pl.pcols.size();
+    if (npc) {
+      C->h_phead.ensure((size_t)W * COL_P_MAX * sizeof(fe));
+      C->phead.ensure((size_t)W * COL_P_MAX * sizeof(fe));
+      fe* hp = C->h_phead.at<fe>();
+      for (uint32_t y = 0; y < npc; y++) memcpy(hp + (size_t)y * R, src.col(pl.pcols[y]), R * sizeof(fe));
+      HIPCHECK(hipMemcpyAsync(C->phead.p, hp, (size_t)npc * R * sizeof(fe), hipMemcpyHostToDevice, s));
+      const size_t stride = (size_t)B * LDE_P_MAX;
+      C->psmall.ensure((size_t)npc * stride * sizeof(fe));
+      for (uint32_t a = 0; a < npc;) {  // one small-LDE launch per period present
+        uint32_t b = a;
+        while (b < npc && pl.pper[b] == pl.pper[a]) b++;
+        launch_periodic_lde(C->phead.f() + (size_t)a * R, R, true, n, N, m.pcols + a, b - a, pl.pper[a], C->roots.f(),
+                            C->iroots.f(), Ntab, C->opow.f(), coef, C->psmall.f() + (size_t)a * stride, stride, s);
+        a = b;
+      }
+      launch_periodic_tile(C->psmall.f(), stride, m.pcols, m.pbp, npc, N, split, lde, s);
+    }
+  }
+  book.commit(coef, lde, n, N, W);
+  st.cols_general = ng;
+  st.cols_periodic = npc;
+  st.cols_zero = W - ng - npc;
+  st.bytes_pinned = (big ? 0 : (uint64_t)ng * col_bytes) + (uint64_t)npc * R * sizeof(fe);
+  st.bytes_dma = (uint64_t)ng * col_bytes + (uint64_t)npc * R * sizeof(fe);
+  C->up_stats = st;
+  C->up_ms = ms_since(t0);
+  if (getenv("ZKL_UP_DEBUG"))
+    fprintf(stderr, "[zkl upload] %u cols x %zu rows: loop %.2f ms on %u threads (slot waits %.2f ms), %u zero / %u periodic / "
+            "%u general, %u chunks\n", W, n, C->up_ms, nt, wait_ms, st.cols_zero, st.cols_periodic, st.cols_general, st.chunks);
+  return split;
+}
+
 // the proof bytes are left in C->proof_s (zkl_hip_last_proof), valid until the next proof
-void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t W, uint32_t n32,
+// d_trace_in: the resident trace, or with hsrc (a host trace) unused
+void prove_impl(zkl_ctx* C, const void* d_trace_in, const ColSource* hsrc, uint32_t W, uint32_t n32,
                 const zkl_air_public_inputs& pi, const zkl_proof_options& o) {
+  const bool trace_on_host = hsrc != nullptr;
   const InFlight in_flight;
   const auto t_call0 = std::chrono::steady_clock::now();
   hipStream_t s = C->stream;
@@ -622,9 +855,12 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   };
   // Column structure: the scan classes every column of this proof's trace (nothing is kept from
   // an earlier proof's trace); zero columns skip the transforms, and the row hash resumes the
-  // partitions whose leading absorb blocks are structured from a table.  A host trace is scanned
-  // chunk by chunk behind its upload and keeps the dense LDE (its chunks are queued before any
-  // class could come back without stalling the upload); only its row hash uses the classes.
+  // partitions whose leading absorb blocks are structured from a table.  A host trace is classed
+  // by the host threads that stage it (trace_lde_host_columns) and takes the same structured LDE.
+  // Only a trace DMA'd from where it lies (a pinned trace buffer, ZKL_UP_MODE=direct), which
+  // nothing reads on the host, is scanned chunk by chunk behind its upload and keeps the dense
+  // LDE (its chunks are queued before any class could come back without stalling the upload);
+  // only its row hash, DEEP and OOD use the classes.
   const bool colstruct = column_structure_enabled();
   ZeroBook& book = C->zero_known;
   ColMeta meta;  // null lists: the later readers walk every column
@@ -641,12 +877,18 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
     period.resize(W);
     decode_column_scan(hbits, W, n, period.data());
   };
-  if (trace_on_host) {
+  const bool direct = trace_on_host && host_trace_direct(C, *hsrc, W, n);
+  if (trace_on_host && !direct) {
+    KScope k(C, KF_NTT);
+    period.resize(W);
+    split = trace_lde_host_columns(C, book, *hsrc, W, n, N, colstruct, C->coef.f(), C->lde.f(), g_lde_split,
+                                   period.data(), &meta, s);
+  } else if (trace_on_host) {
     KScope k(C, KF_NTT);
     book.begin(C->coef.p, C->lde.p, n, N, W);
     book.all_unknown();  // the upload writes every coef column
     if (colstruct) HIPCHECK(hipMemsetAsync(C->scanbits.p, 0, (size_t)W * sizeof(uint32_t), s));
-    upload_trace_chunked(C, d_trace_in, W, n, s, [&](uint32_t c0, uint32_t nc) {
+    upload_trace_direct(C, hsrc->base, W, n, s, [&](uint32_t c0, uint32_t nc) {
       if (colstruct) launch_scan_columns(C->coef.f() + (size_t)c0 * n, nc, n, (uint32_t*)C->scanbits.p + c0, s, false);
       lde_cols(c0, nc, nullptr);
     });
@@ -669,7 +911,7 @@ void prove_impl(zkl_ctx* C, const void* d_trace_in, bool trace_on_host, uint32_t
   // ---- trace commitment (commit_to_rows + MerkleTree)
   C->parts.ensure((size_t)o.num_partitions * N * sizeof(fe) + N * sizeof(fe));
   C->tree.ensure(2 * N * sizeof(fe));
-  if (colstruct && trace_on_host) {
+  if (colstruct && direct) {
     // the dense LDE wrote exact zeros for the zero columns: DEEP and OOD get the lists here too
     read_scan();
     ZeroBook none;
@@ -1348,13 +1590,24 @@ void preflight_or_throw(zkl_ctx* C, const fe* d_trace, uint32_t W, uint32_t n32,
   if (C->report.kind) throw InvalidArg(report_message(C->report));
 }
 
-// the host trace whole into the context's resident copy
-const fe* upload_trace_whole(zkl_ctx* C, const zkl_f128* trace, uint32_t W, uint32_t n32) {
-  const size_t bytes = (size_t)W * n32 * sizeof(fe);
+// the host trace whole into the context's resident copy (a null column cleared)
+const fe* upload_trace_whole(zkl_ctx* C, const ColSource& src, uint32_t W, uint32_t n32) {
+  const size_t n = n32, bytes = (size_t)W * n * sizeof(fe);
   C->trace.ensure(bytes);
-  HIPCHECK(hipMemcpyAsync(C->trace.p, trace, bytes, hipMemcpyHostToDevice, C->stream));
+  if (src.base && src.stride == n) {
+    HIPCHECK(hipMemcpyAsync(C->trace.p, src.base, bytes, hipMemcpyHostToDevice, C->stream));
+  } else {
+    for (uint32_t c = 0; c < W; c++) {
+      fe* dst = C->trace.f() + (size_t)c * n;
+      if (const fe* p = src.col(c)) HIPCHECK(hipMemcpyAsync(dst, p, n * sizeof(fe), hipMemcpyHostToDevice, C->stream));
+      else HIPCHECK(hipMemsetAsync(dst, 0, n * sizeof(fe), C->stream));
+    }
+  }
   HIPCHECK(hipStreamSynchronize(C->stream));  // the caller's memory is pageable: read before we return to it
   return C->trace.f();
+}
+const fe* upload_trace_whole(zkl_ctx* C, const zkl_f128* trace, uint32_t W, uint32_t n32) {
+  return upload_trace_whole(C, ColSource{nullptr, (const fe*)trace, n32}, W, n32);
 }
 
 int run_guarded(zkl_ctx* ctx, const std::function<void()>& f) {
@@ -1662,6 +1915,22 @@ const char* zkl_hip_last_error(const zkl_ctx* c) { return c ? c->err.c_str() : g
 
 void zkl_hip_free(uint8_t* p) { free(p); }
 
+// a host trace, flat or as column pointers; caller holds c->mu
+static void prove_host_source(zkl_ctx* c, const ColSource& src, uint32_t width, uint32_t n,
+                              const zkl_air_public_inputs& pi, const zkl_proof_options& o) {
+  if (c->preflight) {  // whole upload, check, then prove from the resident copy
+    validate_request(width, n, pi, o);
+    const fe* d = upload_trace_whole(c, src, width, n);
+    c->up_stats = zkl_upload_stats{};
+    c->up_stats.cols_general = width;  // nothing was classified on the host
+    c->up_stats.bytes_dma = (uint64_t)width * n * sizeof(fe);
+    preflight_or_throw(c, d, width, n, pi, o);
+    prove_impl(c, d, nullptr, width, n, pi, o);
+    return;
+  }
+  prove_impl(c, nullptr, &src, width, n, pi, o);
+}
+
 static int finish_proof(std::vector<uint8_t>& v, uint8_t** out, size_t* len) {
   uint8_t* b = (uint8_t*)malloc(v.size());
   if (!b) return ZKL_E_OOM;
@@ -1678,14 +1947,24 @@ int zkl_hip_prove_segment(zkl_ctx* c, const zkl_f128* trace, uint32_t width, uin
   c->proof_s.clear();
   int rc = run_guarded(c, [&] {
     HIPCHECK(hipSetDevice(c->device));
-    if (c->preflight) {  // whole upload, check, then prove from the resident copy
-      validate_request(width, n, *pi, *o);
-      const fe* d = upload_trace_whole(c, trace, width, n);
-      preflight_or_throw(c, d, width, n, *pi, *o);
-      prove_impl(c, d, false, width, n, *pi, *o);
-      return;
-    }
-    prove_impl(c, trace, true, width, n, *pi, *o);
+    prove_host_source(c, ColSource{nullptr, (const fe*)trace, n}, width, n, *pi, *o);
+  });
+  return rc ? rc : finish_proof(c->proof_s, proof, len);
+}
+
+int zkl_hip_prove_segment_columns(zkl_ctx* c, const zkl_f128* const* columns, uint32_t width, uint32_t n,
+                                  const zkl_air_public_inputs* pi, const zkl_proof_options* o, uint8_t** proof,
+                                  size_t* len) {
+  if (!c || !columns || !pi || !o || !proof || !len) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->proof_s.clear();
+  int rc = run_guarded(c, [&] {
+    // `width` pointers are read: the layout's width is checked before the first one is
+    validate_request(width, n, *pi, *o);
+    if (trace_layout_width(*pi, width) != (int)width)
+      throw InvalidArg("trace width does not match the layout implied by the feature mask");
+    HIPCHECK(hipSetDevice(c->device));
+    prove_host_source(c, ColSource{(const fe* const*)columns, nullptr, 0}, width, n, *pi, *o);
   });
   return rc ? rc : finish_proof(c->proof_s, proof, len);
 }
@@ -1699,7 +1978,7 @@ int zkl_hip_prove_segment_device(zkl_ctx* c, const void* d_trace, uint32_t width
   int rc = run_guarded(c, [&] {
     HIPCHECK(hipSetDevice(c->device));
     if (c->preflight) preflight_or_throw(c, (const fe*)d_trace, width, n, *pi, *o);
-    prove_impl(c, d_trace, false, width, n, *pi, *o);
+    prove_impl(c, d_trace, nullptr, width, n, *pi, *o);
   });
   return rc ? rc : finish_proof(c->proof_s, proof, len);
 }
@@ -1736,7 +2015,7 @@ int zkl_hip_prove_segment_device_into(zkl_ctx* c, const void* d_trace, uint32_t 
   int rc = run_guarded(c, [&] {
     HIPCHECK(hipSetDevice(c->device));
     if (c->preflight) preflight_or_throw(c, (const fe*)d_trace, width, n, *pi, *o);
-    prove_impl(c, d_trace, false, width, n, *pi, *o);
+    prove_impl(c, d_trace, nullptr, width, n, *pi, *o);
   });
   return rc ? rc : copy_last_proof(c, buf, cap, len);
 }
@@ -2130,6 +2409,46 @@ int zkl_hip_lde_columns(zkl_ctx* c, const void* d_values, uint32_t nc, uint32_t 
     HIPCHECK(hipStreamSynchronize(s));
     if (split_out) *split_out = split;
   });
+}
+
+int zkl_hip_lde_columns_host(zkl_ctx* c, const zkl_f128* const* columns, uint32_t nc, uint32_t n, uint32_t blowup,
+                             int want_split, void* d_coeffs, void* d_lde, uint32_t* period_out, int* split_out) {
+  if (!c || !columns || !d_coeffs || !d_lde || nc == 0 || nc > 4096 || n < 2 || (n & (n - 1)) || blowup < 2 ||
+      (blowup & (blowup - 1)))
+    return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return run_guarded(c, [&] {
+    HIPCHECK(hipSetDevice(c->device));
+    const size_t N = (size_t)n * blowup;
+    ensure_tables(c, n, N);
+    std::vector<uint32_t> per(nc, COL_GENERAL);
+    const int split = trace_lde_host_columns(c, c->zero_stage, ColSource{(const fe* const*)columns, nullptr, 0}, nc, n, N,
+                                             column_structure_enabled(), (fe*)d_coeffs, (fe*)d_lde, want_split != 0,
+                                             per.data(), nullptr, c->stream);
+    check_launch("stage entry point");
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (period_out) std::copy(per.begin(), per.end(), period_out);
+    if (split_out) *split_out = split;
+  });
+}
+
+int zkl_classify_columns(const zkl_f128* const* columns, uint32_t nc, uint32_t n, uint32_t* period_out) {
+  if (!columns || !period_out || nc == 0 || n == 0 || (n & (n - 1))) return ZKL_E_INVALID;
+  for (uint32_t c = 0; c < nc; c++) period_out[c] = classify_column((const fe*)columns[c], n);
+  return ZKL_OK;
+}
+
+int zkl_hip_upload_stats(const zkl_ctx* c, zkl_upload_stats* out) {
+  if (!c || !out) return ZKL_E_INVALID;
+  *out = c->up_stats;
+  return ZKL_OK;
+}
+
+int zkl_hip_set_upload_chunk_columns(zkl_ctx* c, uint32_t k) {
+  if (!c) return ZKL_E_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->up_chunk_cols = k;  // clamped per call to what a slot holds at that call's column length
+  return ZKL_OK;
 }
 
 int zkl_hip_set_ntt_mode(int mode) {

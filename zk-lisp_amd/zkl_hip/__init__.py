@@ -106,6 +106,12 @@ class StepInfo(C.Structure):
     ]
 
 
+class UploadStats(C.Structure):
+    """zkl_upload_stats: what the last host-trace call on a context staged."""
+    _fields_ = [("cols_zero", C.c_uint32), ("cols_periodic", C.c_uint32), ("cols_general", C.c_uint32),
+                ("chunks", C.c_uint32), ("bytes_pinned", C.c_uint64), ("bytes_dma", C.c_uint64)]
+
+
 def _fe_int(v) -> int:
     return v.lo | (v.hi << 64)
 
@@ -178,6 +184,15 @@ def load_library():
     lib.zkl_hip_prove_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                           P(AirPublicInputs), P(ProofOptions), P(P(C.c_uint8)), P(C.c_size_t)]
     lib.zkl_hip_prove_segment_device.argtypes = lib.zkl_hip_prove_segment.argtypes
+    if hasattr(lib, "zkl_hip_prove_segment_columns"):  # (older builds, loaded by scripts/ for A/B, lack these)
+        lib.zkl_hip_prove_segment_columns.argtypes = [C.c_void_p, P(C.c_void_p), C.c_uint32, C.c_uint32,
+                                                      P(AirPublicInputs), P(ProofOptions), P(P(C.c_uint8)),
+                                                      P(C.c_size_t)]
+        lib.zkl_hip_lde_columns_host.argtypes = [C.c_void_p, P(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_int, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_int)]
+        lib.zkl_hip_upload_stats.argtypes = [C.c_void_p, P(UploadStats)]
+        lib.zkl_classify_columns.argtypes = [P(C.c_void_p), C.c_uint32, C.c_uint32, P(C.c_uint32)]
+        lib.zkl_hip_set_upload_chunk_columns.argtypes = [C.c_void_p, C.c_uint32]
     lib.zkl_hip_prove_segment_device_into.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                       P(AirPublicInputs), P(ProofOptions), C.c_void_p, C.c_size_t,
                                                       P(C.c_size_t)]
@@ -754,6 +769,18 @@ class row_zero_mask:
         return False
 
 
+def classify_columns(cols, n_rows: int):
+    """zkl_classify_columns (host only): the class the staging threads give each host column
+    (buffers of n_rows * 16 bytes, or None): 0, a power-of-two period below n_rows, COL_GENERAL."""
+    arr, keep = Context._column_pointers(cols)
+    out = (C.c_uint32 * len(cols))()
+    rc = load_library().zkl_classify_columns(arr, len(cols), n_rows, out)
+    del keep
+    if rc != 0:
+        raise ZklError(rc, "classify_columns: n_rows must be a power of two, at least one column")
+    return list(out)
+
+
 def device_count() -> int:
     lib = load_library()
     n = C.c_int()
@@ -976,6 +1003,54 @@ class Context:
                                             C.byref(out), C.byref(ln))
         return self._finish(rc, out, ln)
 
+    @staticmethod
+    def _column_pointers(cols):
+        """(array of column pointers, the objects that keep them alive): each entry a writable or
+        read-only buffer of n_rows * 16 bytes, an integer address, or None (an all-zero column)."""
+        arr = (C.c_void_p * len(cols))()
+        keep = []
+        for i, col in enumerate(cols):
+            if col is None:
+                arr[i] = None
+            elif isinstance(col, int):
+                arr[i] = col
+            elif isinstance(col, (C.Array, C.Structure)):
+                arr[i] = C.addressof(col)
+                keep.append(col)
+            else:
+                b = (C.c_uint8 * len(col)).from_buffer_copy(col) if isinstance(col, bytes) else \
+                    (C.c_uint8 * memoryview(col).nbytes).from_buffer(col)
+                arr[i] = C.addressof(b)
+                keep.append(b)
+        return arr, keep
+
+    def prove_segment_columns(self, cols, n_rows: int, pi: AirPublicInputs, opts: ProofOptions) -> bytes:
+        """zkl_hip_prove_segment_columns: the proof of prove_segment from separately allocated
+        columns; `cols` is a sequence of per-column host buffers (n_rows * 16 bytes each), or None
+        for an all-zero column."""
+        arr, keep = self._column_pointers(cols)
+        out = C.POINTER(C.c_uint8)()
+        ln = C.c_size_t()
+        rc = self.lib.zkl_hip_prove_segment_columns(self.ptr, arr, len(cols), n_rows, C.byref(pi), C.byref(opts),
+                                                    C.byref(out), C.byref(ln))
+        del keep
+        return self._finish(rc, out, ln)
+
+    def upload_stats(self) -> dict:
+        """zkl_hip_upload_stats of the last host-trace proof or lde_columns_host call."""
+        st = UploadStats()
+        rc = self.lib.zkl_hip_upload_stats(self.ptr, C.byref(st))
+        if rc:
+            self._err(rc)
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def set_upload_chunk_columns(self, k: int = 0):
+        """General columns per staged chunk of the following host-trace calls (0: what a pinned
+        slot holds; larger values are clamped to that)."""
+        rc = self.lib.zkl_hip_set_upload_chunk_columns(self.ptr, k)
+        if rc:
+            self._err(rc)
+
     def trace_buffer(self, nbytes: int, slot: int = 0) -> int:
         """zkl_hip_trace_buffer: address of the context's pinned host trace buffer `slot` (0/1,
         >= nbytes), to be filled in place and passed to prove_segment (DMA'd without a staging
@@ -1170,6 +1245,19 @@ class Context:
         if rc != 0:
             raise ZklError(rc, self._err(rc))
         return sp.value
+
+    def lde_columns_host(self, cols, n_rows, blowup, d_coeffs, d_lde, want_split=False):
+        """zkl_hip_lde_columns_host: the trace LDE stage from host columns (buffers, or None for
+        an all-zero column), classified on the host while staged; returns (classes, split)."""
+        arr, keep = self._column_pointers(cols)
+        per = (C.c_uint32 * len(cols))()
+        sp = C.c_int(0)
+        rc = self.lib.zkl_hip_lde_columns_host(self.ptr, arr, len(cols), n_rows, blowup, 1 if want_split else 0,
+                                               C.c_void_p(d_coeffs), C.c_void_p(d_lde), per, C.byref(sp))
+        del keep
+        if rc != 0:
+            self._err(rc)
+        return list(per), sp.value
 
     def set_kernel_timing(self, mode: int):
         """0: no kernel-family events, 1: trace row hash only (default), 2: every family."""
